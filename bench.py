@@ -113,7 +113,56 @@ def parse():
                          "every rank count, so that N = 1 and N > 1 issue the same launches)")
     ap.add_argument("--check-replicas", action="store_true",
                     help="after the run: sha1 of every rank's G / D / G_ema parameters -> `param_digest`, `replicas_identical`")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step handed its caller as DIR/<name>.npy: the two "
+                         "losses and a fixed, seeded sample of the updated G / D / G_ema weights and of the step's G / D gradients "
+                         "(float32 / float64, at most 64 MB), for comparing two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_SAMPLE = 2 ** 20  # elements kept of a larger output (4 MB in float32): 7 arrays stay far below DUMP_CAP_BYTES
+DUMP_CAP_BYTES = 64 * 2 ** 20
+
+
+def flat_sample(tensors, k=DUMP_SAMPLE, seed=0):
+    """float32 numpy copy of the concatenation of `tensors`, or — when that has more than k elements — of k of its elements
+    drawn without replacement by a seeded generator and kept in index order: the same positions in every run."""
+    import numpy as np
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    if flat.numel() > k:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), size=k, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """Write every array of `arrays` (name -> float32 / float64 numpy array) as out_dir/<name>.npy."""
+    import numpy as np
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > cap:
+        raise ValueError(f"--dump-outputs: {total} bytes > the {cap}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def trainer_outputs(trainer, d_loss, g_loss):
+    """What GifTrainer.step hands its caller after the last step (deferred updates flushed): the two losses, the updated weights
+    of G, D and G_ema and (in p.grad) the gradients of that step; the weight and gradient sets as fixed samples (flat_sample,
+    one seed per set)."""
+    import numpy as np
+    out = {"d_loss": np.asarray(d_loss.item(), np.float64), "g_loss": np.asarray(g_loss.item(), np.float64)}
+    for seed, (name, m) in enumerate((("G", trainer.G), ("D", trainer.D), ("G_ema", trainer.G_ema))):
+        out[name + "_weights"] = flat_sample(list(m.parameters()), seed=seed)
+    for seed, (name, bk) in enumerate((("G", trainer.g_bucket), ("D", trainer.d_bucket)), start=3):
+        out[name + "_grads"] = flat_sample([p.grad for p in bk.params], seed=seed)
+    return out
 
 
 def _pick_threads(threads):
@@ -574,7 +623,7 @@ def main():
         if sampled:  # instrument this step's launches (the events are read after the timed region)
             ops.prof_enable(True)
             prof_steps += 1
-        run_step(it, data[k % len(data)])
+        last = run_step(it, data[k % len(data)])
         if sampled:
             ops.prof_enable(False)
         it += 1
@@ -587,6 +636,9 @@ def main():
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt, comm_ms = t[0].item(), t[1].item()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer_outputs(trainer, *last))
 
     replicas = {"ranks": world, "backend": dist.get_backend() if use_dist else None}
     if args.check_replicas or world > 1:  # (always with > 1 rank: the digests are what shows that the exchange kept the replicas equal)

@@ -30,3 +30,30 @@ def test_first_r1_iteration_is_a_warmup_step(steps, warmup, r1_every):
     process (buffer allocation, kernel loading)."""
     warm, timed = _r1_steps(steps, warmup, r1_every)
     assert warm == [warmup - 1] and timed and timed[0] == r1_every - 1
+
+
+def test_flat_sample_is_fixed_and_complete_below_the_sample_size():
+    """--dump-outputs: a small output is written whole, a large one as the same seeded positions in every run."""
+    import numpy as np
+    import torch
+    small = [torch.arange(6.0).view(2, 3), torch.ones(4, dtype=torch.float64)]
+    assert np.array_equal(bench.flat_sample(small, k=16), np.r_[np.arange(6.0), np.ones(4)].astype(np.float32))
+    big = [torch.randn(300, generator=torch.Generator().manual_seed(1)), torch.randn(50, 7, generator=torch.Generator().manual_seed(2))]
+    a, b = bench.flat_sample(big, k=64, seed=3), bench.flat_sample([t.clone() for t in big], k=64, seed=3)
+    assert a.dtype == np.float32 and a.shape == (64,) and np.array_equal(a, b)
+    whole = torch.cat([t.reshape(-1) for t in big]).numpy()
+    assert np.isin(a, whole).all() and len(np.unique(a)) == 64, "distinct elements of the output"
+    assert not np.array_equal(a, bench.flat_sample(big, k=64, seed=4))
+
+
+def test_dump_outputs_writes_float_npy_files_under_the_cap(tmp_path):
+    import numpy as np
+    arrays = {"loss": np.asarray(0.25, np.float64), "w": np.arange(10, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    assert sorted(os.listdir(tmp_path / "out")) == ["loss.npy", "w.npy"]
+    assert np.load(tmp_path / "out" / "loss.npy") == 0.25 and np.array_equal(np.load(tmp_path / "out" / "w.npy"), arrays["w"])
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "bad"), {"idx": np.arange(3)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), arrays, cap=40)
+    assert bench.DUMP_SAMPLE * 4 * 5 + 16 <= bench.DUMP_CAP_BYTES, "five sampled sets + two losses fit the cap"

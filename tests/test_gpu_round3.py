@@ -406,6 +406,28 @@ def test_bench_single_rank_collective_code_path_and_line_contract():
     assert rr.get("error") is None and rr["unit"] == "GB/s" and rr["Mtri_per_s"] > 0 and rr["cpu_baseline"]["value"] > 0
 
 
+def test_bench_dump_outputs_same_in_two_processes(tmp_path):
+    """bench.py --dump-outputs: the last timed step's losses and the sampled weights / gradients come out as float .npy files under
+    the size cap, and two processes with the same arguments write the same arrays (the default step has no atomics)."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "64",
+                              "--batch", "8", "--vocab", "64", "--r1-every", "2", "--no-cpu-baseline", "--no-prof", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=900, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["D_grads", "D_weights", "G_ema_weights", "G_grads", "G_weights", "d_loss", "g_loss"]
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), f"{k} differs between two runs with the same arguments"
+    assert a["G_grads"].any() and a["D_grads"].any() and not np.array_equal(a["G_weights"], a["G_ema_weights"])
+
+
 # ------------------------------------------------------------------------------------------------ advisor findings of round 2
 def test_f16_gradient_store_saturation_raises_the_overflow_flag():
     """f16 activation stores clamp at +-65504: an overflowing activation GRADIENT would never reach the loss scaler as inf.  The

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from golden import make_reference_parity_golden as P  # noqa: E402
 from golden.make_resize_golden import CASES  # noqa: E402
 from oracle import resize_ref as R  # noqa: E402
 
@@ -39,14 +40,12 @@ def test_explicit_taps_partition_unity_and_identity():
         assert np.abs(R.resize_explicit(x, (6, 9), mode) - x).max() < 1e-6  # same size = identity
 
 
-@pytest.mark.reference
 def test_oracle_equals_imported_reference():
-    from oracle import reference_import as ri
-    if not ri.available():
-        pytest.skip("/root/reference not mounted")
-    f = ri.reference_fast_image_reshape()
-    x = torch.rand(2, 3, 13, 10, generator=torch.Generator().manual_seed(5))
+    """The oracle against outputs of the real function (tests/golden/make_reference_parity_golden.py)."""
+    gold = torch.load(os.path.join(os.path.dirname(__file__), "golden", "reference_parity_golden.pt"), weights_only=True)
+    x = P.inputs()
+    assert P.checksums(x) == gold["input_checksums"]
     for mode in ("bicubic", "bilinear"):
         for clamp in (False, True):
-            assert torch.equal(f(x, 21, 6, non_diff_allowed=clamp, mode=mode),
-                               R.fast_image_reshape(x, 21, 6, non_diff_allowed=clamp, mode=mode))
+            assert torch.equal(gold["resize"][f"{mode}_{clamp}"],
+                               R.fast_image_reshape(x["resize_x"], 21, 6, non_diff_allowed=clamp, mode=mode))

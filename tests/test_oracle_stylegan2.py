@@ -1,16 +1,16 @@
-"""Pins oracle/stylegan2_ref.py: (a) against golden vectors produced by the real reference
-(tests/golden/make_stylegan2_golden.py) — runs everywhere; (b) against the real reference modules imported in
-place — build container only (marker `reference`)."""
-import contextlib
-import io
+"""Pins oracle/stylegan2_ref.py against golden vectors produced by the real reference: model-level forward and gradients
+(tests/golden/make_stylegan2_golden.py) and forward parity of models and layers (tests/golden/make_reference_parity_golden.py)."""
 import os
+import sys
 
-import pytest
 import torch
 
-from oracle import stylegan2_ref as R
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from golden import make_reference_parity_golden as P  # noqa: E402
+from oracle import stylegan2_ref as R  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "stylegan2_golden.pt")
+PARITY = os.path.join(os.path.dirname(__file__), "golden", "reference_parity_golden.pt")
 
 
 def _gold():
@@ -92,48 +92,38 @@ def test_upfirdn2d_shapes_and_edge_cases():
     assert torch.allclose(R.upfirdn2d(ones, k, pad=(2, 2))[0, 0, 3:6, 3:6], torch.ones(3, 3), atol=1e-6)
 
 
-@pytest.mark.reference
+def _parity():
+    """Outputs of the real reference modules and the inputs they were computed on (tests/golden/make_reference_parity_golden.py)."""
+    gold = torch.load(PARITY, weights_only=True)
+    x = P.inputs()
+    assert P.checksums(x) == gold["input_checksums"], "regenerated inputs differ from the ones the stored outputs were computed on"
+    return gold, x
+
+
 def test_oracle_equals_imported_reference():
-    from oracle import reference_import as ri
-    SG, D, L = ri.reference_modules()
-    with contextlib.redirect_stdout(io.StringIO()):
-        g = SG(embedding_vocab_size=20, rendered_flame_ascondition=True, normal_maps_as_cond=True)
-        d = D(size=64, num_color_chnls=9)
-    sd = R.seeded_state_dict(g.state_dict(), 5)
-    g.load_state_dict(sd, strict=True)
-    cond = torch.rand(2, 6, 64, 64) * 2 - 1
+    gold, x = _parity()
+    gold = gold["stylegan2"]
+    sd = R.seeded_state_dict(P.template_sd(gold["g_template"]), P.G_SEED)
+    with torch.no_grad():  # stored outputs of another CPU (other ATen conv kernels): a few ulps of the |out| <= 3.2 image,
+        for idx, ref in zip((torch.tensor([1, 19]), x["z"]), gold["g_out"]):  # the bound of test_generator_config1_shape_golden
+            assert (R.generator_forward(sd, x["cond"], 4, idx) - ref).abs().max() < 1e-5
+    sdd = R.seeded_state_dict(P.template_sd(gold["d_template"]), P.D_SEED)
     with torch.no_grad():
-        for idx in (torch.tensor([1, 19]), torch.randn(2, 512)):
-            ref = g(cond, None, step=4, alpha=1, input_indices=idx)[0]
-            assert (R.generator_forward(sd, cond, 4, idx) - ref).abs().max() < 1e-6
-    sdd = R.seeded_state_dict(d.state_dict(), 6)
-    d.load_state_dict(sdd, strict=True)
-    img = torch.rand(4, 3, 64, 64) * 2 - 1
-    c2 = torch.rand(4, 6, 64, 64) * 2 - 1
-    with torch.no_grad():
-        assert (R.discriminator_forward(sdd, img, c2, 64) - d(img, condition=c2)[0]).abs().max() < 1e-6
+        assert (R.discriminator_forward(sdd, x["img"], x["d_cond"], 64) - gold["d_scores"]).abs().max() < 1e-6
     # layer-level: upfirdn2d incl. negative pads, FusedLeakyReLU
-    k = L.make_kernel([1, 3, 3, 1])
-    x = torch.randn(2, 5, 9, 9)
-    for up, down, pad in ((1, 1, (2, 2)), (2, 1, (2, 1)), (1, 2, (1, 1)), (1, 1, (-1, 2)), (2, 2, (3, 0))):
-        assert torch.equal(R.upfirdn2d(x, k, up, down, pad), L.upfirdn2d(x, k, up, down, pad))
+    k = R.make_kernel([1, 3, 3, 1])
+    assert torch.equal(k, gold["fir_kernel"])
+    for (up, down, pad), ref in zip(P.UPFIRDN_CASES, gold["fir_out"]):
+        assert torch.equal(R.upfirdn2d(x["fir_x"], k, up, down, pad), ref)
 
 
-@pytest.mark.reference
 def test_oracle_layer_variants_equal_imported_reference():
     """Less-travelled layer options: down-sampling modulated conv, no-demod 1x1 (ToRGB), up-sampling modulated conv."""
-    from oracle import reference_import as ri
-    _, _, L = ri.reference_modules()
-    torch.manual_seed(3)
-    x, st = torch.randn(2, 16, 8, 8), torch.randn(2, 512)
-    for kw in (dict(downsample=True), dict(upsample=True), dict()):
-        m = L.ModulatedConv2d(16, 24, 3, 512, **kw)
-        sd = m.state_dict()
-        ref = m(x, st)
-        got = R.modulated_conv2d(x, sd["weight"], sd["modulation.weight"], sd["modulation.bias"], st, True,
-                                 kw.get("upsample", False), sd.get("blur.kernel"), kw.get("downsample", False))
+    gold, x = _parity()
+    gold = gold["modulated_conv"]
+    for i, (kw, t, ref) in enumerate(zip(P.MODCONV_CASES, gold["templates"], gold["out"])):
+        _, demod, up, down = P.modconv_args(kw)
+        sd = R.seeded_state_dict(P.template_sd(t), P.MODCONV_SEED + i)
+        got = R.modulated_conv2d(x["mc_x"], sd["weight"], sd["modulation.weight"], sd["modulation.bias"], x["mc_style"], demod,
+                                 up, sd.get("blur.kernel"), down)
         assert ref.shape == got.shape and (ref - got).abs().max() < 1e-5, kw
-    m = L.ModulatedConv2d(16, 3, 1, 512, demodulate=False)
-    sd = m.state_dict()
-    assert (m(x, st) - R.modulated_conv2d(x, sd["weight"], sd["modulation.weight"], sd["modulation.bias"], st,
-                                          demodulate=False)).abs().max() < 1e-5

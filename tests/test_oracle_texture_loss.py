@@ -25,23 +25,19 @@ def test_oracle_reproduces_reference_values(tag):
     assert len(R.all_pairs(6)) == 10
 
 
-@pytest.mark.reference
 def test_oracle_equals_imported_reference_losses():
-    """R1 and the pairwise texture loss of the oracle vs the REAL loss_functions.losses (imported in place)."""
-    import types
-    from oracle import reference_import as ri
+    """R1 and the pairwise texture loss of the oracle vs values of the REAL loss_functions.losses
+    (tests/golden/make_reference_parity_golden.py)."""
+    from golden import make_reference_parity_golden as P
     from oracle import stylegan2_ref as S
-    if not ri.available():
-        pytest.skip("/root/reference not mounted")
-    L = ri.reference_losses()
+    gold_all = torch.load(os.path.join(os.path.dirname(__file__), "golden", "reference_parity_golden.pt"), weights_only=True)
+    ref = gold_all["losses"]
+    xs = P.inputs()
+    assert P.checksums(xs) == gold_all["input_checksums"]
     g = gold()
     tex = torch.from_numpy(g["textures"])
-    me = types.SimpleNamespace(face_region_only_mask=torch.from_numpy(g["face_big"]))
-    assert torch.equal(L.InterpolatedTextureLoss.pairwise_texture_loss(me, tex[2], tex[3]),
-                       R.pairwise_texture_loss(torch.from_numpy(g["face_big"]), tex[2], tex[3]))
-    x = torch.randn(3, 3, 8, 8, requires_grad=True)
-    w = torch.randn(3, 8, 8)
-    out = (x * w).sum((1, 2, 3)).pow(2)[:, None]
-    ref = L.grad_penalty_loss([x], out, step=None)
+    assert torch.equal(ref["pair23_big"], R.pairwise_texture_loss(torch.from_numpy(g["face_big"]), tex[2], tex[3]))
+    x = xs["r1_x"].clone().requires_grad_(True)
+    out = (x * xs["r1_w"]).sum((1, 2, 3)).pow(2)[:, None]
     got = S.grad_penalty_loss([x], out)
-    assert torch.allclose(ref, got, rtol=1e-6, atol=0)
+    assert torch.allclose(ref["r1"], got, rtol=1e-6, atol=0)
