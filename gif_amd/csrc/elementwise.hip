@@ -623,7 +623,9 @@ __global__ void __launch_bounds__(1024) sqnorm_kernel(const float* __restrict__ 
     __shared__ float red[16];
     const float* gb = g + (size_t)blockIdx.x * n;
     float acc = 0.f;
-    long n4 = n >> 2;
+    // rows after the first start 16-byte aligned only when n % 4 == 0 (or the base is offset to match): float4 loads then,
+    // otherwise the whole row takes the scalar loop
+    const long n4 = (reinterpret_cast<uintptr_t>(gb) & 15) == 0 ? n >> 2 : 0;
     for (long i = threadIdx.x; i < n4; i += blockDim.x) {
         float4 v = reinterpret_cast<const float4*>(gb)[i];
         acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
@@ -1059,7 +1061,7 @@ int gif_bilinear_down_f32(const float* x, float* y, int B, int R, int S, int C, 
 int gif_mbstd_fwd_f32(const float* x, float* y, float* stat, int B, int H, int W, int C, int Cy, int G,
                       gif_stream_t stream) {
     GIF_REQUIRE(x && y && stat && B > 0 && G >= 1 && G <= 8 && B % G == 0, "mbstd: batch %d not divisible by group %d", B, G);
-    GIF_REQUIRE(C > 0 && Cy >= C + 1 && Cy % 4 == 0, "mbstd: bad channel counts C=%d Cy=%d", C, Cy);
+    GIF_REQUIRE(C > 0 && C % 4 == 0 && Cy >= C + 1 && Cy % 4 == 0, "mbstd: C and Cy must be multiples of 4 (C=%d Cy=%d)", C, Cy);
     hipStream_t s = gif::as_stream(stream);
     int M = B / G;
     mbstd_stat_kernel<<<M, 256, 0, s>>>(x, stat, M, G, (long)H * W * C);
@@ -1071,7 +1073,7 @@ int gif_mbstd_fwd_f32(const float* x, float* y, float* stat, int B, int H, int W
 int gif_mbstd_bwd_f32(const float* x, const float* gy, float* gx, int B, int H, int W, int C, int Cy, int G,
                       gif_stream_t stream) {
     GIF_REQUIRE(x && gy && gx && B > 0 && G >= 1 && G <= 8 && B % G == 0, "mbstd_bwd: bad batch/group");
-    GIF_REQUIRE(C > 0 && Cy >= C + 1, "mbstd_bwd: bad channel counts");
+    GIF_REQUIRE(C > 0 && C % 4 == 0 && Cy >= C + 1, "mbstd_bwd: C must be a multiple of 4 and Cy >= C + 1 (C=%d Cy=%d)", C, Cy);
     int M = B / G;
     mbstd_bwd_kernel<<<M, 256, 0, gif::as_stream(stream)>>>(x, gy, gx, M, G, H * W, C, Cy);
     return gif::check_launch("mbstd_bwd");

@@ -135,6 +135,9 @@ __global__ void __launch_bounds__(64 * SK_WAVES) skinny_nn_kernel(const SkinnyPa
                 const f32x4 d = (n < p.N && a_ok) ? *reinterpret_cast<const f32x4*>(ap2 + 8 * (c0 + u)) : (f32x4)(0.f);
                 av[u] *= d * d * d;
             }
+            // columns [N, pad4(N)) of A (and A2) are read but outside the operand: exact zeros, so a NaN / Inf there cannot reach C
+#pragma unroll
+            for (int t = 0; t < 4; ++t) av[u][t] = n + t < p.N ? av[u][t] : 0.f;
 #pragma unroll
             for (int t = 0; t < 4; ++t) bv[u][t] = (n + t < p.N && b_ok) ? bp[(size_t)(n + t) * p.ldb] : 0.f;
         }

@@ -597,6 +597,8 @@ def bias_act_bwd(gy, y, want_gbias, slope=0.2, gain=2 ** 0.5):
     npix = B * H * W
     gx = empty_nhwc(B, C, H, W, y.device, y.dtype)
     gbias = partial = None
+    if npix == 0:  # nothing to launch: the bias gradient of an empty batch is zero
+        return gx, (torch.zeros((C,), device=y.device, dtype=torch.float32) if want_gbias else None)
     if want_gbias:
         gbias = torch.empty((C,), device=y.device, dtype=torch.float32)
         partial = torch.empty((lib.gif_colsum_partial_floats(npix, C),), device=y.device, dtype=torch.float32)
@@ -611,6 +613,8 @@ def colsum(x):
     x = nhwc(x)
     B, C, H, W = x.shape
     npix = B * H * W
+    if npix == 0:  # nothing to launch: a sum over no rows
+        return torch.zeros((C,), device=x.device, dtype=torch.float32)
     out = torch.empty((C,), device=x.device, dtype=torch.float32)
     partial = torch.empty((lib.gif_colsum_partial_floats(npix, C),), device=x.device, dtype=torch.float32)
     _lib.check(_fn("colsum", x.dtype)(x.data_ptr(), out.data_ptr(), partial.data_ptr(), npix, C, _stream()), "colsum")
@@ -624,6 +628,8 @@ def mul_reduce(a, b, scale=None, want_scaled=False):
     _same_dtype(a, b, "mul_reduce")
     B, C, H, W = a.shape
     assert b.shape == a.shape
+    if B * H * W == 0:  # nothing to launch
+        return torch.zeros((B, C), device=a.device, dtype=torch.float32), (empty_nhwc(B, C, H, W, a.device, a.dtype) if want_scaled else None)
     nchunk = lib.gif_mul_reduce_chunks(H * W)
     out = torch.empty((B, C), device=a.device, dtype=torch.float32)
     partial = torch.empty((B * nchunk * C,), device=a.device, dtype=torch.float32)
@@ -692,6 +698,8 @@ def act_inv_mul_reduce(g, y, residual, bias, slope, gain):
     g, y = nhwc(g), nhwc(y)
     _same_dtype(g, y, "act_inv_mul_reduce")
     B, C, H, W = y.shape
+    if B * H * W == 0:  # nothing to launch
+        return torch.zeros((B, C), device=y.device, dtype=torch.float32)
     nchunk = lib.gif_mul_reduce_chunks(H * W)
     out = torch.empty((B, C), device=y.device, dtype=torch.float32)
     partial = torch.empty((B * nchunk * C,), device=y.device, dtype=torch.float32)

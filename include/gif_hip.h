@@ -410,7 +410,7 @@ int gif_demod_wgrad_f32(const float* w, const float* g_wsq, float* gw, int cout,
 
 /* ------------------------------------------------------------------------------------------------
  * Minibatch standard deviation — replaces stg2_discriminator.py:59-65.
- * x [B,H,W,C] -> y [B,H,W,Cy] (Cy >= C+1): y[..., :C] = x, y[..., C] = stat[b % M], rest 0, with
+ * x [B,H,W,C] -> y [B,H,W,Cy] (C % 4 == 0, Cy >= C+1; forward: Cy % 4 == 0): y[..., :C] = x, y[..., C] = stat[b % M], rest 0, with
  * M = B/G, stat[m] = mean_{c,h,w} sqrt(var_{g}(x[g*M+m]) + 1e-8) (biased variance over the G members).
  * stat [M] is also returned for the backward.
  * ---------------------------------------------------------------------------------------------- */
