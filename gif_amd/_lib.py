@@ -64,7 +64,11 @@ PROTOTYPES = {
     "gif_rasterize_colors_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "gif_rasterize_f64": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "gif_rasterize_colors_f64": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "gif_rasterize_colors_bwd_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "gif_rasterize_colors_bwd_f32": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "gif_vertex_normals_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
+    "gif_vertex_normals_bwd_f32": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    "gif_face_gather_bwd_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
     "gif_texture_map_f32": (c_int, [P] * 9 + [c_int] * 6 + [P]),
     "gif_texture_map_bwd_f32": (c_int, [P] * 8 + [c_int] * 6 + [P]),
     "gif_conv_epilogue_ws_floats": (c_i64, [c_i64, c_int]),

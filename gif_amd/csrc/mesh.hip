@@ -19,16 +19,13 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {  // torch.cross component orde
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 
-// entry = face * 4 + corner ; off[v] .. off[v+1] are the entries of vertex v
-__global__ void __launch_bounds__(256) vertex_normals_kernel(const float* __restrict__ verts,
-                                                             const int32_t* __restrict__ faces,
-                                                             const int32_t* __restrict__ off,
-                                                             const int32_t* __restrict__ ent, float* __restrict__ out,
-                                                             int B, int V) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * V) return;
-    int b = (int)(i / V), v = (int)(i - (long)b * V);
-    const float* vb = verts + (size_t)b * V * 3;
+__device__ __forceinline__ V3 add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 scale(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+
+// unnormalised normal of vertex v: its CSR entries (face * 4 + corner) in order, off[v] .. off[v+1]
+__device__ __forceinline__ V3 vertex_sum(const float* __restrict__ vb, const int32_t* __restrict__ faces,
+                                         const int32_t* __restrict__ off, const int32_t* __restrict__ ent, int v) {
     float nx = 0.f, ny = 0.f, nz = 0.f;
     for (int e = off[v]; e < off[v + 1]; ++e) {
         int f = ent[e] >> 2, c = ent[e] & 3;
@@ -39,12 +36,113 @@ __global__ void __launch_bounds__(256) vertex_normals_kernel(const float* __rest
         else n = cross(sub(p1, p0), sub(p2, p0));              // :31-32
         nx += n.x; ny += n.y; nz += n.z;
     }
+    return {nx, ny, nz};
+}
+
+__global__ void __launch_bounds__(256) vertex_normals_kernel(const float* __restrict__ verts,
+                                                             const int32_t* __restrict__ faces,
+                                                             const int32_t* __restrict__ off,
+                                                             const int32_t* __restrict__ ent, float* __restrict__ out,
+                                                             int B, int V) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * V) return;
+    int b = (int)(i / V), v = (int)(i - (long)b * V);
+    const V3 n = vertex_sum(verts + (size_t)b * V * 3, faces, off, ent, v);
     // F.normalize(normals, eps=1e-6, dim=1): x / max(||x||_2, eps)   (:34)
-    float len = sqrtf(nx * nx + ny * ny + nz * nz);
+    float len = sqrtf(n.x * n.x + n.y * n.y + n.z * n.z);
     float d = fmaxf(len, 1e-6f);
-    out[i * 3 + 0] = nx / d;
-    out[i * 3 + 1] = ny / d;
-    out[i * 3 + 2] = nz / d;
+    out[i * 3 + 0] = n.x / d;
+    out[i * 3 + 1] = n.y / d;
+    out[i * 3 + 2] = n.z / d;
+}
+
+// Backward, step 1 (per vertex): through x / max(||x||, eps).  ||x|| >= eps: (g - n (n.g)) / ||x|| with n = x / ||x||;
+// clamped (||x|| < eps, e.g. a vertex whose faces are all degenerate): g / eps.
+__global__ void __launch_bounds__(256) vertex_normals_bwd_norm(const float* __restrict__ verts,
+                                                               const int32_t* __restrict__ faces,
+                                                               const int32_t* __restrict__ off,
+                                                               const int32_t* __restrict__ ent,
+                                                               const float* __restrict__ gout, float* __restrict__ gsum,
+                                                               int B, int V) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * V) return;
+    int b = (int)(i / V), v = (int)(i - (long)b * V);
+    const V3 x = vertex_sum(verts + (size_t)b * V * 3, faces, off, ent, v);
+    const V3 g = ld3(gout + i * 3);
+    const float len = sqrtf(x.x * x.x + x.y * x.y + x.z * x.z);
+    V3 r;
+    if (len >= 1e-6f) {
+        const float inv = 1.f / len;
+        const V3 n = scale(x, inv);
+        r = scale(sub(g, scale(n, dot(n, g))), inv);
+    } else {
+        r = scale(g, 1.f / 1e-6f);
+    }
+    gsum[i * 3 + 0] = r.x;
+    gsum[i * 3 + 1] = r.y;
+    gsum[i * 3 + 2] = r.z;
+}
+
+// Backward, step 2 (per vertex, gather over its CSR entries in order): for an entry (f, c) the derivative of face f's
+// three corner cross products with respect to its corner c.  n = cross(a, b) => da = cross(b, gn), db = cross(gn, a).
+__global__ void __launch_bounds__(256) vertex_normals_bwd_gather(const float* __restrict__ verts,
+                                                                 const int32_t* __restrict__ faces,
+                                                                 const int32_t* __restrict__ off,
+                                                                 const int32_t* __restrict__ ent,
+                                                                 const float* __restrict__ gsum, float* __restrict__ gverts,
+                                                                 int B, int V) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * V) return;
+    int b = (int)(i / V), v = (int)(i - (long)b * V);
+    const float* vb = verts + (size_t)b * V * 3;
+    const float* gb = gsum + (size_t)b * V * 3;
+    V3 acc = {0.f, 0.f, 0.f};
+    for (int e = off[v]; e < off[v + 1]; ++e) {
+        const int f = ent[e] >> 2, c = ent[e] & 3;
+        const int i0 = faces[3 * f + 0], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+        const V3 p0 = ld3(vb + 3 * i0), p1 = ld3(vb + 3 * i1), p2 = ld3(vb + 3 * i2);
+        const V3 g0 = ld3(gb + 3 * i0), g1 = ld3(gb + 3 * i1), g2 = ld3(gb + 3 * i2);
+        V3 d[3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+        {  // corner 1: cross(p2 - p1, p0 - p1)
+            const V3 a = sub(p2, p1), bb = sub(p0, p1);
+            const V3 ga = cross(bb, g1), gbb = cross(g1, a);
+            d[2] = add(d[2], ga); d[0] = add(d[0], gbb); d[1] = sub(d[1], add(ga, gbb));
+        }
+        {  // corner 2: cross(p0 - p2, p1 - p2)
+            const V3 a = sub(p0, p2), bb = sub(p1, p2);
+            const V3 ga = cross(bb, g2), gbb = cross(g2, a);
+            d[0] = add(d[0], ga); d[1] = add(d[1], gbb); d[2] = sub(d[2], add(ga, gbb));
+        }
+        {  // corner 0: cross(p1 - p0, p2 - p0)
+            const V3 a = sub(p1, p0), bb = sub(p2, p0);
+            const V3 ga = cross(bb, g0), gbb = cross(g0, a);
+            d[1] = add(d[1], ga); d[2] = add(d[2], gbb); d[0] = sub(d[0], add(ga, gbb));
+        }
+        acc = add(acc, d[c]);
+    }
+    gverts[i * 3 + 0] = acc.x;
+    gverts[i * 3 + 1] = acc.y;
+    gverts[i * 3 + 2] = acc.z;
+}
+
+// Backward of a face gather ([B,V,C] -> [B,F,3,C], C = 3): per vertex, the sum of its CSR entries' (face, corner) gradients
+// in CSR order — deterministic, no atomics (the transpose of standard_rasterize.face_vertices).
+__global__ void __launch_bounds__(256) face_gather_bwd_kernel(const float* __restrict__ gface,
+                                                              const int32_t* __restrict__ off,
+                                                              const int32_t* __restrict__ ent, float* __restrict__ gvert,
+                                                              int B, int V, int F) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * V) return;
+    int b = (int)(i / V), v = (int)(i - (long)b * V);
+    const float* gf = gface + (size_t)b * F * 9;
+    V3 acc = {0.f, 0.f, 0.f};
+    for (int e = off[v]; e < off[v + 1]; ++e) {
+        const int f = ent[e] >> 2, c = ent[e] & 3;
+        acc = add(acc, ld3(gf + 9 * f + 3 * c));
+    }
+    gvert[i * 3 + 0] = acc.x;
+    gvert[i * 3 + 1] = acc.y;
+    gvert[i * 3 + 2] = acc.z;
 }
 
 }  // namespace
@@ -57,6 +155,30 @@ extern "C" int gif_vertex_normals_f32(const float* verts, const int32_t* faces, 
     vertex_normals_kernel<<<gif::cdiv((long)B * V, 256), 256, 0, gif::as_stream(stream)>>>(verts, faces, csr_off, csr_ent,
                                                                                             normals, B, V);
     return gif::check_launch("vertex_normals");
+}
+
+extern "C" int gif_vertex_normals_bwd_f32(const float* verts, const int32_t* faces, const int32_t* csr_off,
+                                          const int32_t* csr_ent, const float* grad_normals, float* work, float* grad_verts,
+                                          int B, int V, int F, gif_stream_t stream) {
+    GIF_REQUIRE(B >= 0 && V > 0 && F >= 0, "vertex_normals_bwd: bad dims");
+    if (B == 0) return 0;
+    GIF_REQUIRE(verts && faces && csr_off && csr_ent && grad_normals && work && grad_verts, "vertex_normals_bwd: null pointer");
+    GIF_REQUIRE(work != grad_verts && work != grad_normals, "vertex_normals_bwd: work must not alias an operand");
+    hipStream_t s = gif::as_stream(stream);
+    const int grid = gif::cdiv((long)B * V, 256);
+    vertex_normals_bwd_norm<<<grid, 256, 0, s>>>(verts, faces, csr_off, csr_ent, grad_normals, work, B, V);
+    vertex_normals_bwd_gather<<<grid, 256, 0, s>>>(verts, faces, csr_off, csr_ent, work, grad_verts, B, V);
+    return gif::check_launch("vertex_normals_bwd");
+}
+
+extern "C" int gif_face_gather_bwd_f32(const float* grad_face, const int32_t* csr_off, const int32_t* csr_ent,
+                                       float* grad_vertex, int B, int V, int F, gif_stream_t stream) {
+    GIF_REQUIRE(B >= 0 && V > 0 && F >= 0, "face_gather_bwd: bad dims");
+    if (B == 0) return 0;
+    GIF_REQUIRE(grad_face && csr_off && csr_ent && grad_vertex, "face_gather_bwd: null pointer");
+    face_gather_bwd_kernel<<<gif::cdiv((long)B * V, 256), 256, 0, gif::as_stream(stream)>>>(grad_face, csr_off, csr_ent,
+                                                                                             grad_vertex, B, V, F);
+    return gif::check_launch("face_gather_bwd");
 }
 
 // ---------------------------------------------------------------------------------------------------------------

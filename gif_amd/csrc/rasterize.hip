@@ -450,3 +450,173 @@ int gif_rasterize_colors_f64(const double* face_vertices, const double* face_col
     return run<double>(face_vertices, face_colors, depth, tri, images, B, F, H, W, workspace, stream, "rasterize_colors_f64");
 }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Backward of the barycentric colour interpolation (gif_rasterize_colors_bwd_f32).  The forward wrote, per pixel (x, y) won
+// by face f (tri[b,y,x] = f), img = sum_k w_k c_{f,k} with w = (1-u-v, v, u) from bary_at; this pass recomputes w from the
+// face vertices and the tri buffer (the forward stores no barycentrics) and forms, per face,
+//   d c_{f,k,ch} = sum_pixels w_k g_ch
+//   d p_{f,j}.xy = sum_pixels sum_k (g . c_{f,k}) dw_k/dp_j     (chain rule through bary_at's dot products; z: 0)
+// The gradient lives inside the winning face only: depth and coverage only select the winner.  Degenerate faces
+// (inverDeno = 0, w = (1,0,0) constant) get no vertex gradient.
+// Deterministic two-pass reduction, no float atomics:
+//   pass 1 (raster_colors_bwd_band): one wave per (image, face, 64-row band of the face's bounding box): each lane walks the
+//          band's pixels of the box with stride 64 in raster order, then a fixed xor butterfly sums the 64 lanes; the 15
+//          sums (6 vertex xy + 9 colour) are the (face, band) partial.  A wave walks at most 64 rows x W pixels, so a
+//          screen-filling face is split over H/64 waves instead of serialising one.
+//   pass 2 (raster_colors_bwd_reduce): one lane per (image, face) adds its bands' partials in band order and writes the
+//          face's gradients (zeros for a face that won no pixel).
+// Both passes take the band range from bwd_bands (same function, same bits), so no partial is read that was not written.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kBwdWaves = 4;   // waves (faces) per pass-1 workgroup
+constexpr int kBwdSums = 15;   // 6 vertex xy + 9 colour sums
+constexpr int kBwdStride = 16; // floats per (face, band) partial
+
+// rows [*r0, *r1] of the face's clamped bounding box, in bands of kTile rows: [*b0, *b1]; b1 < b0 if the face shades nothing
+__device__ __forceinline__ void bwd_bands(const Face<float>& f, int H, int W, int& x_min, int& x_max, int& y_min, int& y_max,
+                                          int& b0, int& b1) {
+    b0 = 0; b1 = -1;
+    x_min = 0; x_max = -1; y_min = 0; y_max = -1;
+    if (!front_facing(f)) return;  // raster_bin never lists it: it wins no pixel
+    face_bbox(f, H, W, x_min, x_max, y_min, y_max);
+    if (x_min > x_max || y_min > y_max) return;
+    b0 = y_min / kTile; b1 = y_max / kTile;
+}
+
+__global__ void __launch_bounds__(kBwdWaves * 64)
+raster_colors_bwd_band(const float* __restrict__ fv, const float* __restrict__ fc, const int32_t* __restrict__ tri,
+                       const float* __restrict__ g, float* __restrict__ part, int F, int H, int W, int bands) {
+    const int lane = threadIdx.x & 63;
+    const int fi = blockIdx.x * kBwdWaves + (threadIdx.x >> 6), band = blockIdx.y, b = blockIdx.z;
+    if (fi >= F) return;  // whole wave: fi is uniform across it
+    const long fo = (long)b * F + fi;
+    const Face<float> f = load_face(fv + fo * 9);
+    int x_min, x_max, y_min, y_max, b0, b1;
+    bwd_bands(f, H, W, x_min, x_max, y_min, y_max, b0, b1);
+    if (band < b0 || band > b1) return;
+    const int r0 = max(y_min, band * kTile), r1 = min(y_max, band * kTile + kTile - 1);
+    const int cols = x_max - x_min + 1, n = (r1 - r0 + 1) * cols;
+    const BaryCtx<float> c = bary_setup(f);
+    const float* cl = fc + fo * 9;  // [3 verts][3 channels]
+    float c9[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c9[k] = cl[k];
+    float acc[kBwdSums];
+#pragma unroll
+    for (int k = 0; k < kBwdSums; ++k) acc[k] = 0.f;
+    const long img = (long)b * H * W;
+    for (int p = lane; p < n; p += 64) {
+        const int y = r0 + p / cols, x = x_min + p % cols;
+        const long gp = img + (long)y * W + x;
+        if (tri[gp] != fi) continue;
+        const float g0 = g[gp * 3 + 0], g1 = g[gp * 3 + 1], g2 = g[gp * 3 + 2];
+        // bary_at, with its intermediates kept
+        const float v2x = (float)x - f.x0, v2y = (float)y - f.y0;
+        const float dot02 = c.v0x * v2x + c.v0y * v2y;
+        const float dot12 = c.v1x * v2x + c.v1y * v2y;
+        const float u = (c.dot11 * dot02 - c.dot01 * dot12) * c.inv;
+        const float v = (c.dot00 * dot12 - c.dot01 * dot02) * c.inv;
+        const float w[3] = {1.f - u - v, v, u};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc[6 + 3 * k + 0] += w[k] * g0;
+            acc[6 + 3 * k + 1] += w[k] * g1;
+            acc[6 + 3 * k + 2] += w[k] * g2;
+        }
+        if (c.inv == 0.f) continue;  // degenerate: w is constant
+        float gw[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gw[k] = g0 * c9[3 * k] + g1 * c9[3 * k + 1] + g2 * c9[3 * k + 2];
+        const float gu = gw[2] - gw[0], gv = gw[1] - gw[0];
+        // u = Nu * inv, v = Nv * inv, inv = 1 / den, den = dot00 * dot11 - dot01^2
+        const float gNu = gu * c.inv, gNv = gv * c.inv;
+        const float gden = -(gu * u + gv * v) * c.inv;
+        const float g00 = gden * c.dot11 + gNv * dot12;
+        const float g11 = gden * c.dot00 + gNu * dot02;
+        const float g01 = -2.f * gden * c.dot01 - gNu * dot12 - gNv * dot02;
+        const float g02 = gNu * c.dot11 - gNv * c.dot01;
+        const float g12 = gNv * c.dot00 - gNu * c.dot01;
+        // dot00 = v0.v0, dot01 = v0.v1, dot11 = v1.v1, dot02 = v0.v2, dot12 = v1.v2; v0 = p2-p0, v1 = p1-p0, v2 = P-p0
+        const float gv0x = 2.f * g00 * c.v0x + g01 * c.v1x + g02 * v2x, gv0y = 2.f * g00 * c.v0y + g01 * c.v1y + g02 * v2y;
+        const float gv1x = 2.f * g11 * c.v1x + g01 * c.v0x + g12 * v2x, gv1y = 2.f * g11 * c.v1y + g01 * c.v0y + g12 * v2y;
+        const float gv2x = g02 * c.v0x + g12 * c.v1x, gv2y = g02 * c.v0y + g12 * c.v1y;
+        acc[0] -= gv0x + gv1x + gv2x; acc[1] -= gv0y + gv1y + gv2y;  // p0
+        acc[2] += gv1x; acc[3] += gv1y;                              // p1
+        acc[4] += gv0x; acc[5] += gv0y;                              // p2
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1)
+#pragma unroll
+        for (int k = 0; k < kBwdSums; ++k) acc[k] += __shfl_xor(acc[k], m, 64);
+    if (lane == 0) {
+        float* o = part + (fo * bands + band) * kBwdStride;
+#pragma unroll
+        for (int k = 0; k < kBwdSums; ++k) o[k] = acc[k];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+raster_colors_bwd_reduce(const float* __restrict__ fv, const float* __restrict__ part, float* __restrict__ gfv,
+                         float* __restrict__ gfc, int B, int F, int H, int W, int bands) {
+    const long fo = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (fo >= (long)B * F) return;
+    const Face<float> f = load_face(fv + fo * 9);
+    int x_min, x_max, y_min, y_max, b0, b1;
+    bwd_bands(f, H, W, x_min, x_max, y_min, y_max, b0, b1);
+    float s[kBwdSums];
+#pragma unroll
+    for (int k = 0; k < kBwdSums; ++k) s[k] = 0.f;
+    for (int band = b0; band <= b1; ++band) {
+        const float* pp = part + (fo * bands + band) * kBwdStride;
+#pragma unroll
+        for (int k = 0; k < kBwdSums; ++k) s[k] += pp[k];
+    }
+    if (gfv) {
+        float* o = gfv + fo * 9;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            o[3 * j + 0] = s[2 * j];
+            o[3 * j + 1] = s[2 * j + 1];
+            o[3 * j + 2] = 0.f;  // depth only selects the winner
+        }
+    }
+    if (gfc) {
+        float* o = gfc + fo * 9;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[k] = s[6 + k];
+    }
+}
+
+int bwd_bands_per_image(int H) { return (H + kTile - 1) / kTile; }
+
+}  // namespace
+
+extern "C" {
+
+int64_t gif_rasterize_colors_bwd_workspace_bytes(int B, int F, int H, int W) {
+    if (B <= 0 || F <= 0 || H <= 0 || W <= 0) return 8;
+    return (int64_t)B * F * bwd_bands_per_image(H) * kBwdStride * 4;
+}
+
+int gif_rasterize_colors_bwd_f32(const float* face_vertices, const float* face_colors, const int32_t* tri,
+                                 const float* grad_images, float* grad_face_vertices, float* grad_face_colors, int B, int F,
+                                 int H, int W, void* workspace, gif_stream_t stream) {
+    GIF_REQUIRE(B >= 0 && F >= 0 && H > 0 && W > 0, "rasterize_colors_bwd: bad dims B=%d F=%d H=%d W=%d", B, F, H, W);
+    if ((long)B * F == 0) return 0;
+    GIF_REQUIRE(face_vertices && face_colors && tri && grad_images && workspace, "rasterize_colors_bwd: null pointer");
+    GIF_REQUIRE(grad_face_vertices || grad_face_colors, "rasterize_colors_bwd: no output");
+    GIF_REQUIRE(((uintptr_t)workspace & 3) == 0, "rasterize_colors_bwd: workspace must be 4-byte aligned");
+    const int bands = bwd_bands_per_image(H);
+    GIF_REQUIRE(B <= 65535 && bands <= 65535 && (long)B * F * bands * kBwdStride < (1L << 40),
+                "rasterize_colors_bwd: too many images / faces");
+    hipStream_t s = gif::as_stream(stream);
+    float* part = reinterpret_cast<float*>(workspace);
+    raster_colors_bwd_band<<<dim3((unsigned)gif::cdiv(F, kBwdWaves), (unsigned)bands, (unsigned)B), kBwdWaves * 64, 0, s>>>(
+        face_vertices, face_colors, tri, grad_images, part, F, H, W, bands);
+    raster_colors_bwd_reduce<<<gif::cdiv((long)B * F, 256), 256, 0, s>>>(face_vertices, part, grad_face_vertices,
+                                                                          grad_face_colors, B, F, H, W, bands);
+    return gif::check_launch("rasterize_colors_bwd");
+}
+}

@@ -160,12 +160,37 @@ int gif_rasterize_colors_f64(const double* face_vertices, const double* face_col
                              int32_t* tri, double* images, int B, int F, int H, int W, void* workspace,
                              gif_stream_t stream);
 
+/* Backward of gif_rasterize_colors_f32 (differentiable condition rendering; no counterpart in the reference, whose rasteriser
+ * has no backward).  face_vertices / face_colors [B,F,3,3] and tri [B,H,W] as the forward used and left them; grad_images
+ * [B,H,W,3] = dL/d images.  Writes, for every face (zeros for a face that won no pixel):
+ *   grad_face_colors   [B,F,3,3]: sum over the face's pixels of w_k * g
+ *   grad_face_vertices [B,F,3,3]: x, y = sum over the face's pixels of sum_k (g . c_k) dw_k/dp_j; z = 0
+ * with the barycentrics w recomputed from face_vertices by the forward's formula (inverDeno = 0: w constant, no vertex
+ * gradient).  The gradient lives inside the winning face only: no silhouette or occlusion-boundary terms.  Either output
+ * may be null (not written).  Deterministic: per (face, 64-row band of its bounding box) partial sums in a fixed order, then a
+ * per-face sum over the bands in band order; no float atomics.  `workspace`: gif_rasterize_colors_bwd_workspace_bytes(B, F,
+ * H, W) bytes, 4-byte aligned, no initialisation needed. */
+int64_t gif_rasterize_colors_bwd_workspace_bytes(int B, int F, int H, int W);
+int gif_rasterize_colors_bwd_f32(const float* face_vertices, const float* face_colors, const int32_t* tri,
+                                 const float* grad_images, float* grad_face_vertices, float* grad_face_colors, int B, int F,
+                                 int H, int W, void* workspace, gif_stream_t stream);
+
 /* Per-vertex normals — replaces vertex_normals() model/mesh_and_3d_helpers.py:5-37 (condition-render pipeline,
  * SURVEY §8(f) row 1).  verts [B,V,3]; faces [F,3] int32 (topology shared by the batch); csr_off [V+1] / csr_ent [3F]:
  * vertex -> entries (face*4 + corner), ordered corner 1, corner 2, corner 0 with faces ascending (the order of the
  * reference's three index_add_ passes); normals [B,V,3] = normalize(sum of face cross products, eps 1e-6). */
 int gif_vertex_normals_f32(const float* verts, const int32_t* faces, const int32_t* csr_off, const int32_t* csr_ent,
                            float* normals, int B, int V, int F, gif_stream_t stream);
+/* Backward of gif_vertex_normals_f32: grad_normals [B,V,3] -> grad_verts [B,V,3] (same verts / faces / CSR as the forward).
+ * Per vertex the normalisation backward (the clamped branch, g / eps, where ||sum|| < 1e-6), then per vertex a gather over
+ * its CSR entries of the cross-product derivatives: deterministic, no atomics.  work: B*V*3 floats of scratch (no aliasing). */
+int gif_vertex_normals_bwd_f32(const float* verts, const int32_t* faces, const int32_t* csr_off, const int32_t* csr_ent,
+                               const float* grad_normals, float* work, float* grad_verts, int B, int V, int F,
+                               gif_stream_t stream);
+/* Backward of the face gather vertices [B,V,3] -> face_vertices [B,F,3,3] (standard_rasterize.face_vertices):
+ * grad_vertex[b,v] = sum over v's CSR entries (face*4 + corner) of grad_face[b,face,corner], in CSR order (no atomics). */
+int gif_face_gather_bwd_f32(const float* grad_face, const int32_t* csr_off, const int32_t* csr_ent, float* grad_vertex,
+                            int B, int V, int F, gif_stream_t stream);
 
 /* Texture stealing — replaces FlameTextureSpace.compute_texture_map (model/stg2_generator.py:378-421):
  * per (sample, UV texel) barycentric 3-D point -> orthographic projection (y flipped) -> bilinear fetch of the source image
