@@ -462,3 +462,114 @@ def test_interpolate_flame_labels_and_synthetic_flame_fixtures():
     n = len(td["valid_pixel_ids"])
     assert td["valid_pixel_3d_faces"].shape == (n, 3) and td["valid_pixel_b_coords"].shape == (n, 3)
     assert abs(n / 64 ** 2 - 0.5) < 0.05 and np.allclose(td["valid_pixel_b_coords"].sum(1), 1, atol=1e-5)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tests/test_gpu_render_edges.py: every hand-written fp64 restatement it bounds the kernels with agrees with ATen's float64 result
+# (F.interpolate, F.grid_sample, F.normalize) or with fp64 autograd, at every row of its tables — a wrong restatement cannot bless a
+# wrong kernel.  No GPU.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _agree12(a, b, what):
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    d = (a - b).abs().max().item() if a.numel() else 0.0
+    assert d <= 1e-12, f"{what}: restatement and ATen float64 differ by {d:.3e}"
+
+
+def _edges():
+    import test_gpu_render_edges as E
+    return E
+
+
+@pytest.mark.parametrize("mode", ["bilinear", "bicubic"])
+@pytest.mark.parametrize("name", ["rs_1x1", "rs_1x9_h4", "rs_2x3", "rs_3x3_up16", "rs_identity", "rs_down_16", "rs_9x12", "rs_33x31",
+                                  "rs_exact_4x6", "rs_planes1", "rs_view_2x3", "rs_gridcap"])
+def test_render_edges_resize_restatement(name, mode):
+    E = _edges()
+    assert name in [r[0] for r in E.RS_ROWS] and len(E.RS_ROWS) == 12 and E.RS_MODES == ["bilinear", "bicubic"]
+    _, _, (Hi, Wi), (Ho, Wo) = next(r for r in E.RS_ROWS if r[0] == name)
+    c = E._resize_case(name, mode)
+    x = c["x"].double().requires_grad_(True)
+    ref = E._interp64(x, (Ho, Wo), mode)
+    (gref,) = torch.autograd.grad(ref, x, c["gy"].double())
+    _agree12(c["fwd"], ref.detach(), f"{name} {mode} forward")
+    _agree12(c["bwd"], gref, f"{name} {mode} backward")
+    assert (c["R"] >= ref.detach().abs() - 1e-12).all() and (c["Rb"] >= gref.abs() - 1e-12).all()
+    if mode == "bilinear":  # weights >= 0: R is the operation itself on |x|
+        _agree12(c["R"], E._interp64(c["x"].double().abs(), (Ho, Wo), mode), f"{name} R")
+    assert c["exact"] == (E._is_pow2(Hi, Ho) and E._is_pow2(Wi, Wo)) == (name in ("rs_1x9_h4", "rs_identity", "rs_exact_4x6", "rs_gridcap"))
+    if not c["exact"]:
+        assert torch.isfinite(c["S"]).all() and (c["S"] >= 0).all() and (c["Sb"] >= 0).all() and c["Sb"].shape == gref.shape
+
+
+@pytest.mark.parametrize("mode", ["bilinear", "bicubic"])
+def test_render_edges_tap_derivatives(mode):
+    """d weight / d coordinate of _taps (what S is built from) against a central difference, wherever no tap index flips."""
+    E = _edges()
+    for nin, nout in ((2, 9), (3, 16), (16, 5), (9, 31), (33, 8), (31, 64)):
+        idx, w, dw, mag, wr = E._taps(nin, nout, mode)
+        h = 1e-6
+        (ip, wp, _, _, _), (im, wm, _, _, _) = E._taps(nin, nout, mode, h), E._taps(nin, nout, mode, -h)
+        same = ((ip == im).all(1) & (ip == idx).all(1))
+        if mode == "bilinear":
+            same &= (nin / nout * (torch.arange(nout) + 0.5) - 0.5 - 2 * h * mag) > 0  # past the src < 0 clamp
+        assert same.sum() >= nout // 2
+        fd = (wp - wm) / (2 * h * mag[:, None])
+        assert ((fd - dw).abs()[same] < 1e-6).all(), (nin, nout, (fd - dw).abs()[same].max())
+        assert (w.sum(1) - 1).abs().max() < 1e-12 and dw.sum(1).abs().max() < 1e-12  # a partition of unity
+        assert (wr >= w.abs()).all() if mode == "bicubic" else not wr.any()  # the polynomial on absolute values bounds the weight
+
+
+@pytest.mark.parametrize("name", ["tx_t21_8x8", "tx_t21_8x8_rand", "tx_t16_8x8", "tx_t16_1x1_c4", "tx_t32_5x12_c4", "tx_t32_12x5_c1_rand",
+                                  "tx_t21_12x5_c1", "tx_t21_5x12_b3", "tx_t32_8x8_c4_b3_rand", "tx_t16_1x1_c1_rand"])
+def test_render_edges_texture_restatement(name):
+    E = _edges()
+    assert name in [r[0] for r in E.TX_ROWS] and len(E.TX_ROWS) == 10
+    c = E._tex_case(name)
+    valid = c["tmap"] >= 0
+    assert c["verts"].shape[1] <= 16 and E._tex_grid(c)[0].abs().max() <= 4
+    if c["B"] > 1:  # one mesh, different cameras
+        assert torch.equal(c["verts"][0], c["verts"][1]) and not torch.equal(c["cam"][0], c["cam"][1])
+    for gtex in (c["gtex"].double(), c["gtex"].double() * (~valid).view(1, 1, c["T"], c["T"])):
+        ref, mask, gref, gabs = E._tex_reference(c, gtex)
+        r = E._tex_restated(c, gtex)
+        _agree12(r["fwd"], ref, f"{name} forward")
+        _agree12(r["bwd"], gref, f"{name} backward")
+        _agree12(r["Rb"], gabs, f"{name} backward R")
+        assert (r["R"] >= ref.abs() - 1e-12).all() and (r["S"] >= 0).all() and (r["Sb"] >= 0).all()
+    if c["exact"]:
+        E._tex_named_ok(c, r["ntaps"])
+    # the map is what the row's comment says: 256-texel workgroups all valid / all invalid / mixed
+    wg = [valid[i:i + 256] for i in range(0, len(valid), 256)]
+    kind = next(r_[5] for r_ in E.TX_ROWS if r_[0] == name)
+    if kind == "wg2_invalid":
+        assert len(wg) == 2 and len(wg[1]) == 185 and not wg[1].any() and wg[0].any() and not wg[0].all()
+    elif kind == "all":
+        assert len(wg) == 1 and wg[0].all()
+    else:
+        assert len(wg) == 4 and all(w.view(4, 64).any(1).all() and not w.view(4, 64).all(1).any() for w in wg)
+
+
+@pytest.mark.parametrize("name", ["vn_v255", "vn_v256", "vn_v257", "vn_v85_b3", "vn_v86_b3"])
+def test_render_edges_normals_restatement(name):
+    """The three-pass corner sum equals the sum of the face normals cross(p1 - p0, p2 - p0) over a vertex's faces (each corner's
+    cross product is that normal), accumulated face by face in numpy; x / max(|x|, eps) is F.normalize; the Jacobian behind R is
+    fp64 autograd's."""
+    E = _edges()
+    assert name in [r[0] for r in E.VN_ROWS] and len(E.VN_ROWS) == 5
+    c = E._vn_case(name)
+    x, Rx, n, R = E._vn_restated(c["verts"], c["faces"])
+    v = c["verts"].double().numpy()
+    want = np.zeros_like(v)
+    for f in c["faces"].numpy():
+        nf = np.cross(v[:, f[1]] - v[:, f[0]], v[:, f[2]] - v[:, f[0]])
+        for k in f:
+            want[:, k] += nf
+    _agree12(x, torch.from_numpy(want), f"{name} corner sums")
+    _agree12(n, F.normalize(x, eps=E.EPS, dim=-1), f"{name} normalize")
+    assert (Rx >= x.abs() - 1e-12).all() and (R >= n.abs()).all()
+    pick = torch.tensor([E.VN_FAN, E.VN_TRI, E.VN_ONE[0], E.VN_TINY[0], E.VN_NOFACE[0], c["V"] - 1])
+    xs = x[0, pick]
+    J = torch.autograd.functional.jacobian(lambda t: F.normalize(t, eps=E.EPS, dim=-1), xs)  # [6,3,6,3]
+    J = torch.stack([J[i, :, i, :] for i in range(len(pick))])
+    got = E._normalize_jacobian(xs)
+    assert ((got - J).abs() <= 1e-12 * J.abs().amax(dim=(1, 2), keepdim=True).clamp_min(1)).all()

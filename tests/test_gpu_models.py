@@ -350,7 +350,13 @@ def test_training_trajectory_vs_oracle_trainer():
     iterations, parameters after the Adam steps and the EMA generator.
 
     Adam with beta1 = 0 moves every weight by ~lr * sign(grad) on its first step, so an entry whose gradient is within rounding
-    of zero may move the other way: parameters are compared on the fraction of entries that agree, losses on their values."""
+    of zero may move the other way: parameters are compared on the fraction of entries that agree, losses on their values.
+
+    Size of a sign flip: the first step is lr * g1 / (|g1| + eps) <= lr.  The second is lr * g2 / sqrt(v2 / (1 - beta2^2)) with
+    v2 = beta2 (1 - beta2) g1^2 + (1 - beta2) g2^2, i.e. lr * sqrt(1 + beta2) * g2 / sqrt(beta2 g1^2 + g2^2): up to
+    sqrt(1 + beta2) * lr = 1.41 lr where |g1| << |g2| (the reference alone moves a fifth of progression.1.st_cv2.conv.weight by more
+    than 1.2 lr on step 2).  Two entries that flip on both steps therefore differ by up to 2 (1 + sqrt(1 + beta2)) lr = 4.82 lr, not
+    4 lr; 4.50 lr is observed on one entry of that weight.  The bound keeps the 5 % of slack it had."""
     from oracle import stylegan2_ref as R
     from oracle.train_ref import RefTrainer
     from gif_amd.train_step import GifTrainer
@@ -373,7 +379,8 @@ def test_training_trajectory_vs_oracle_trainer():
         assert abs(d_got.item() - d_ref.item()) < 2e-3 * max(1.0, abs(d_ref.item())), (i, d_got.item(), d_ref.item())
         assert abs(g_got.item() - g_ref.item()) < 2e-3 * max(1.0, abs(g_ref.item())), (i, g_got.item(), g_ref.item())
     lr_g, lr_d = 0.002 * 4 / 5, 0.002 * 16 / 17
-    for model, leaves, lr in ((G, ref.g, lr_g), (D, ref.d, lr_d)):
+    for model, leaves, lr, beta2 in ((G, ref.g, lr_g, 0.99 ** (4 / 5)), (D, ref.d, lr_d, 0.99 ** (16 / 17))):
+        two_flips = 2 * (1 + (1 + beta2) ** 0.5) * lr  # a flip of the first step (lr) and of the second (sqrt(1 + beta2) lr)
         sd = model.state_dict()
         agree, total = 0, 0
         named = dict(model.named_parameters())
@@ -383,7 +390,7 @@ def test_training_trajectory_vs_oracle_trainer():
             diff = (sd[k].detach().cpu() - v.detach()).abs()
             agree += int((diff <= 0.05 * lr).sum())
             total += diff.numel()
-            assert diff.max().item() <= 4.2 * lr, (k, diff.max().item())  # at most two sign flips of lr-sized steps
+            assert diff.max().item() <= 1.05 * two_flips, (k, diff.max().item())  # at most a sign flip on each of the two steps
         print(f"trajectory agreement: {agree / total:.4f} ({total} weights)")
         assert agree / total > 0.985, (agree, total)  # (0.992 observed: 0.8 % of the ~21 M trained weights have |grad| ~ rounding)
     decay = 0.5 ** (32 / 10000)
