@@ -130,7 +130,8 @@ __device__ __forceinline__ float4 load4(const f16* p) {
     return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
 __device__ __forceinline__ void store4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float sat_f16(float v) { return fminf(fmaxf(v, -65504.f), 65504.f); }
+// (comparisons, not fminf / fmaxf: those return their other operand for a NaN, and a NaN would be stored as -65504)
+__device__ __forceinline__ float sat_f16(float v) { return v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v); }
 __device__ __forceinline__ void store4(f16* p, float4 v) {
     f16x4_t h;
     h[0] = (f16)sat_f16(v.x); h[1] = (f16)sat_f16(v.y); h[2] = (f16)sat_f16(v.z); h[3] = (f16)sat_f16(v.w);
@@ -142,8 +143,8 @@ __device__ __forceinline__ void store4(f16* p, float4 v) {
 __device__ __forceinline__ void store4_flag(float* p, float4 v, unsigned*) { store4(p, v); }
 __device__ __forceinline__ void store4_flag(f16* p, float4 v, unsigned* flag) {
     if (flag) {
-        const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-        if (!(m <= 65504.f)) atomicOr(flag, 1u);  // also true for NaN
+        // one comparison per element: each is false for a NaN (a maximum over the four would drop a NaN beside a finite value)
+        if (!(fabsf(v.x) <= 65504.f && fabsf(v.y) <= 65504.f && fabsf(v.z) <= 65504.f && fabsf(v.w) <= 65504.f)) atomicOr(flag, 1u);
     }
     store4(p, v);
 }

@@ -573,3 +573,91 @@ def test_render_edges_normals_restatement(name):
     J = torch.stack([J[i, :, i, :] for i in range(len(pick))])
     got = E._normalize_jacobian(xs)
     assert ((got - J).abs() <= 1e-12 * J.abs().amax(dim=(1, 2), keepdim=True).clamp_min(1)).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The fp64 restatements of tests/test_gpu_pointwise_edges.py, tied to ATen float64 / the oracle within 1e-12.  No GPU.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _pointwise():
+    import test_gpu_pointwise_edges as P
+    return P
+
+
+def test_pointwise_edges_pack_reference():
+    """pack_ref is a zero tensor with the two sources written at their offsets, and its adjoint per source is the channel slice."""
+    P = _pointwise()
+    for row in P.PK_ROWS:
+        name, B, H, W, C0, off0, C1, off1, cp, v0, v1 = row
+        if B * H * W > 4096:
+            continue
+        g = P._rng(row)
+        a = torch.randn(B, C0, H, W, generator=g, dtype=torch.float64)
+        b = torch.randn(B, C1, H, W, generator=g, dtype=torch.float64) if C1 else None
+        want = torch.zeros(B, cp, H, W, dtype=torch.float64)
+        want[:, off0:off0 + C0] = a
+        if b is not None:
+            want[:, off1:off1 + C1] = b
+        got = P.pack_ref(a, b, off0, off1, cp)
+        _agree12(got, want, f"{name} pack_ref")
+        gy = torch.randn(B, cp, H, W, generator=g, dtype=torch.float64)
+        rhs = (a * gy[:, off0:off0 + C0]).sum() + (0 if b is None else (b * gy[:, off1:off1 + C1]).sum())
+        assert abs((got * gy).sum() - rhs) <= 1e-12 * (got.abs() * gy.abs()).sum()
+
+
+def test_pointwise_edges_texture_loss_restatement():
+    """tex_loss64 is the oracle's pairwise_texture_loss on the textures times the common visibility mask; tex_grad_R bounds the
+    autograd gradient and keeps (1 + s) where the gradient has (1 - s)."""
+    from oracle import texture_loss_ref as TL
+    P = _pointwise()
+    for row in P.TX_ROWS:
+        name, C, H, W = row[:4]
+        if C * H * W > 4096:
+            continue
+        a, b, ma, mb, f = P._tex_case(row)
+        a64 = a.double().requires_grad_(True)
+        loss, Rl, d, s = P.tex_loss64(a64, b, ma, mb, f)
+        m = torch.ones(H, W, dtype=torch.float64)
+        for t in (ma, mb):
+            m = m if t is None else m * t.double()
+        want = TL.pairwise_texture_loss(f.double()[None], a.double() * m, b.double() * m)
+        assert abs(loss.item() - want.item()) <= 1e-12 and Rl.item() >= abs(loss.item()) - 1e-12
+        (gr,) = torch.autograd.grad(loss, a64)
+        s_, d_ = s.detach(), d.detach()
+        _agree12(gr, f.double() * s_ * (1 - s_) * 2 * d_ * m / d_.numel(), f"{name} gradient formula")
+        assert (P.tex_grad_R(d_, s_, f, 0.37) >= 0.37 * gr.abs() - 1e-300).all()
+        if row[6] == "sat":
+            assert sorted(set((a - b).abs().round().flatten().tolist())) == [0.0, 3.0, 10.0, 1000.0]
+
+
+def test_pointwise_edges_pyramid_tap_rule():
+    """down_tap_mask marks exactly the source pixels with a non-zero weight in fp64 autograd of F.interpolate, each weight 0.25."""
+    P = _pointwise()
+    for name, B, C, R, S in P.BD_ROWS:
+        if R == S or R > 64:
+            continue
+        x = torch.zeros(1, 1, R, R, dtype=torch.float64, requires_grad=True)
+        y = F.interpolate(x, (S, S), mode="bilinear", align_corners=False)
+        (w,) = torch.autograd.grad(y, x, torch.ones_like(y))
+        mask = P.down_tap_mask(R, S)
+        assert torch.equal(w[0, 0] != 0, mask) and mask.sum().item() == 4 * S * S, name
+        _agree12(w[0, 0], 0.25 * mask.double(), f"{name} tap weights")
+
+
+def test_pointwise_edges_fir_rows_match_the_oracle():
+    """fir64 on every (kernel shape, up, down, pad0, output size, flip) of the generic-kernel rows — non-square kernels, flip = 0,
+    pad0 = 0 and beyond the kernel, outputs past the input: none of which test_fir64_matches_the_oracle covers — is the oracle's
+    upfirdn2d (flip = 0: the oracle given the flipped kernel), cropped to the row's output size; fir_support marks its non-zero
+    outputs for a positive input."""
+    P = _pointwise()
+    for row in P.GF_ROWS:
+        name, B, C, H, W, KH, KW, up, down, pad0, (Ho, Wo), flip, epi = row
+        x, k, _, _ = P._fir_case(row, False)
+        x, k = x.double(), k.double()
+        p1 = max((Ho - 1) * down + KH - (H * up + pad0), (Wo - 1) * down + KW - (W * up + pad0))
+        want = R.upfirdn2d(x, k if flip else torch.flip(k, [0, 1]), up, down, (pad0, p1))[:, :, :Ho, :Wo]
+        got = P.fir64(x, k, up, down, pad0, (Ho, Wo), flip)
+        _agree12(got, want, f"{name} fir64")
+        pos = R.upfirdn2d(torch.ones_like(x), k, up, down, (pad0, p1))[0, 0, :Ho, :Wo]
+        assert torch.equal(pos > 0, P.fir_support(row)), name
+        if flip is False and KH * KW > 1:
+            assert (got - P.fir64(x, k, up, down, pad0, (Ho, Wo), True)).abs().max() > 1e-3, f"{name}: the kernel is symmetric"
