@@ -13,12 +13,14 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "wgrad_route.h"  // which kernel a call gets: every tile / stage / twin / family decision of the host code below
 
 namespace {
 
+namespace route = gif_wgrad;
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int BKP_MAX = 32;  // host-side rounding unit of the pixel chunks (any BKP below divides it)
 
 struct WgradParams {
     const void* sm;   // small side [B,Hs,Ws,Cs]   (fp32, or f16 for the T = f16 instantiation)
@@ -966,23 +968,6 @@ void wgrad_launch(dim3 grid, int threads, hipStream_t s, const WgradParams& p) {
     hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, p);
 }
 
-// GIF_H2_WGRAD_V2=0: the per-wave-split f16x2 kernel (conv_wgrad_mfma<..., 2>) instead of the cooperative pre-split one (A/B)
-inline bool h2v2_on() {
-    static const int on = gif::knob("GIF_H2_WGRAD_V2") ? atoi(gif::knob("GIF_H2_WGRAD_V2")) != 0 : 1;
-    return on != 0;
-}
-// GIF_H2_WGRAD_TAPS=0: the thin-big-side layers on the 128 x 32 per-tap tiles (A/B)
-inline bool thin_taps_on() {
-    static const int on = gif::knob("GIF_H2_WGRAD_TAPS") ? atoi(gif::knob("GIF_H2_WGRAD_TAPS")) != 0 : 1;
-    return on != 0;
-}
-// taps per 128-column tile and the number of column tiles for a thin big side of Cb (<= 32) channels
-inline void thin_tap_tiles(int Cb, int T, int* tpt, int* tgroups) {
-    int n = 128 / Cb;
-    if (n > T) n = T;
-    *tpt = n;
-    *tgroups = (T + n - 1) / n;
-}
 // ------------------------------------------------------------------------------------------------------------------
 // f16x2 weight gradient, third form (round 6): NO raw LDS stage.  profiles/r6_wgrad_nodma_probe.txt: 28-30 % of conv_wgrad_h2v2's time
 // is its per-stage LDS-DMA — the raw fp32 stage is single-buffered (LDS budget of two workgroups per CU), so the DMA of stage s + 1 can
@@ -1363,24 +1348,6 @@ inline void wgrad_launch_v2(bool tab, dim3 grid, hipStream_t s, const WgradParam
     else wgrad_launch_v2_t<false, false>(grid, lds, s, p);
 }
 
-// wgrad tiles follow the SAME row/col padding as the forward packing (gif_conv2d_pack_dims(Cs, Cb)):
-// rows RP multiple of 32 or 128, cols CP multiple of 8 or 32 — so pad further to the tile here.
-inline int tile_of(int c) { return c <= 32 ? 32 : 128; }
-
-// 256x128 tiles (wave tile 128x64: 6 LDS operand reads per 8 MFMAs instead of 4 per 4 — the operand reads, one ds_read_b32 per
-// MFMA operand in this [pixel][channel] layout, are what caps the 128x128 kernel) whenever the row count allows it and the
-// operands go through the plain LDS-DMA path.  GIF_WGRAD_BIG=0 disables it.
-inline bool wgrad_big_tile(int Cs, int Cb, bool scaled, long Ntot) {
-    static int off = -1;
-    if (off < 0) {
-        const char* e = gif::knob("GIF_WGRAD_BIG");
-        off = (e && atoi(e) == 0) ? 1 : 0;
-    }
-    // (below ~16K reduction rows the halved workgroup count costs more than the operand reuse gains: measured)
-    return !off && !scaled && Ntot >= 16384 && tile_of(Cs) == 128 && tile_of(Cb) == 128 && ((Cs + 127) / 128 * 128) % 256 == 0;
-}
-inline int tile_rows(int Cs, int Cb, bool scaled, long Ntot) { return wgrad_big_tile(Cs, Cb, scaled, Ntot) ? 256 : tile_of(Cs); }
-
 template <typename T>
 __global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ wp, int R, int C, int KH,
                                    int KW, int RP, int CP, long sr, long sc, long sky, long skx, float scale) {
@@ -1662,16 +1629,6 @@ __global__ void __launch_bounds__(1024) conv_wgrad_small_mfma(const SmallWgradPa
     }
 }
 
-inline bool small_wgrad_ok(const gif_conv_geom* g, bool scaled) {
-    static int off = -1;
-    if (off < 0) {
-        const char* e = gif::knob("GIF_SMALL_WGRAD");
-        off = (e && atoi(e) == 0) ? 1 : 0;
-    }
-    return !off && !scaled && g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1 && g->Hs == g->Hb && g->Ws == g->Wb &&
-           g->Cs <= 32 && g->Cb <= 16 && (long)g->B * g->Hs * g->Ws >= 65536;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // f16 "halo" weight gradient for the thin high-resolution layers (Cs <= 32, Cb <= 32, stride 1: the 1024^2 block of BASELINE
 // configs[4] and the condition-noise / ToRGB layers, model/stg2_generator.py:159-209, stylegan2_common_layers.py:388-431).
@@ -1870,18 +1827,6 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_halo_f16(const HaloWgradPar
     }
 }
 
-// GIF_F16_HALO_WGRAD=0: A/B knob (the per-tap kernel).  Workgroups (= splits): two per CU, never more than patches.
-inline bool halo_wgrad_ok(const gif_conv_geom* g) {
-    static const int off = gif::knob("GIF_F16_HALO_WGRAD") ? atoi(gif::knob("GIF_F16_HALO_WGRAD")) == 0 : 0;
-    return !off && g->stride == 1 && g->Cs <= 32 && g->Cb <= 32 && g->KH <= 3 && g->KW <= 3 && g->Hs == g->Hb && g->Ws == g->Wb &&
-           g->KH == 2 * g->pad + 1 && g->KW == 2 * g->pad + 1 && g->Hs >= 16 && g->Ws >= 16 &&
-           (long)g->B * gif::cdiv(g->Hs, 16) * gif::cdiv(g->Ws, 16) >= 512;
-}
-inline int halo_wgrad_splits(const gif_conv_geom* g) {
-    const long patches = (long)g->B * gif::cdiv(g->Hs, 16) * gif::cdiv(g->Ws, 16);
-    return (int)(patches < 512 ? patches : 512);
-}
-
 // Winograd F(3x3,2x2) output transform fused with the split reduction: dW = A'^T dU A' with
 // A'^T = [1 1 1 0; 0 1 -1 0; 0 1 1 -1] (the F(3,2) matrix with the sign of the input transform's last row folded in,
 // because V was produced by the F(2,3) input transform whose last row is the negative of F(3,2)'s).
@@ -1925,11 +1870,108 @@ __global__ void wino_unpack_wgrad_kernel(const float* __restrict__ ws, float* __
     }
 }
 
-// wgrad workspace dims: rows/cols padded to the wgrad tile (32 or 128)
-inline void wgrad_dims(int Cs, int Cb, int* RP, int* CP) {
-    int bp = tile_of(Cs), bq = tile_of(Cb);
-    *RP = (Cs + bp - 1) / bp * bp;
-    *CP = (Cb + bq - 1) / bq * bq;
+// ---- host side: knobs -> route (wgrad_route.h) -> launch ---------------------------------------------------------------------------
+// The GIF_* variables of wgrad_route.h, read once per process — except GIF_CONV_VARIANT, which probe scripts set in-process: every call.
+route::WgradKnobs wgrad_knobs() {
+    static const route::WgradKnobs once = [] {
+        route::WgradKnobs k;
+        const auto num = [](const char* name, int unset) { const char* e = gif::knob(name); return e ? atoi(e) : unset; };
+        k.x3_wgrad_thin = num("GIF_X3_WGRAD_THIN", k.x3_wgrad_thin);
+        k.x3_wgrad_simple = num("GIF_X3_WGRAD_SIMPLE", 0) != 0;
+        k.h2_wgrad_plain_tab = num("GIF_H2_WGRAD_PLAIN_TAB", 1) != 0;
+        k.h2_wgrad_v2 = num("GIF_H2_WGRAD_V2", 1) != 0;
+        k.h2_wgrad_taps = num("GIF_H2_WGRAD_TAPS", 1) != 0;
+        k.wgrad_big = num("GIF_WGRAD_BIG", 1) != 0;
+        k.small_wgrad = num("GIF_SMALL_WGRAD", 1) != 0;
+        k.f16_wgrad256 = num("GIF_F16_WGRAD256", 1) != 0;
+        k.f16_halo_wgrad = num("GIF_F16_HALO_WGRAD", 1) != 0;
+        k.f16_halo_wgrad_tr = num("GIF_F16_HALO_WGRAD_TR", 1) != 0;
+        return k;
+    }();
+    route::WgradKnobs k = once;
+    const char* variant = gif::knob("GIF_CONV_VARIANT");
+    k.conv_variant_set = variant != nullptr;
+    k.conv_variant = variant ? atoi(variant) : 0;
+    return k;
+}
+
+route::WgradShape wgrad_shape(const gif_conv_geom* g, bool scaled) {
+    return route::WgradShape{g->B, g->Hb, g->Wb, g->Cb, g->Hs, g->Ws, g->Cs, g->KH, g->KW, g->stride, g->pad, scaled, false};
+}
+
+// launches conv_wgrad_mfma<T, ...> iff `l` names exactly this instantiation
+template <typename T, int BP, int BQ, int WP, int WQ, bool GLDS, int BKP, bool TAB = false, int X3 = 0>
+bool wgrad_try(const route::WgradLaunch& l, dim3 grid, hipStream_t s, const WgradParams& p) {
+    if (l.f16 != (sizeof(T) == 2) || l.BP != BP || l.BQ != BQ || l.WP != WP || l.WQ != WQ || l.GLDS != GLDS || l.BKP != BKP || l.TAB != TAB ||
+        l.X3 != X3)
+        return false;
+    wgrad_launch<T, BP, BQ, WP, WQ, GLDS, BKP, TAB, X3>(grid, l.threads, s, p);
+    return true;
+}
+
+// One tiled launch of a route.  The ladder below is the complete list of conv_wgrad_mfma instantiations the library carries.
+int wgrad_launch_one(const route::WgradLaunch& l, int nsplit, hipStream_t s, const WgradParams& p0) {
+    WgradParams p = p0;
+    if (l.unit_tab) p.stab_nb = 1;
+    p.tpt = l.tpt; p.tgroups = l.tgroups;
+    const dim3 grid((unsigned)(l.wgs_per_split * nsplit));
+    if (l.kernel == route::WGRAD_H2V2) {
+        wgrad_launch_v2(l.TAB, grid, s, p, l.TAPS);
+        return 0;
+    }
+    using gif::f16;
+    const bool launched =
+        l.kernel == route::WGRAD_MFMA &&
+        // f16x2 (per-wave split; the default is conv_wgrad_h2v2)
+        (wgrad_try<float, 128, 32, 2, 1, true, 32, false, 2>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 32, true, 2>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 32, false, 2>(l, grid, s, p) ||
+         // bf16x3
+         wgrad_try<float, 128, 32, 4, 1, true, 32, false, 1>(l, grid, s, p) ||
+         wgrad_try<float, 128, 32, 2, 1, true, 32, false, 1>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 32, true, 1>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 16, true, 1>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 32, false, 1>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 16, false, 1>(l, grid, s, p) ||
+         // native fp32 MFMA
+         wgrad_try<float, 256, 128, 2, 2, true, 16>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 16, true>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 16>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, true, 32>(l, grid, s, p) ||
+         wgrad_try<float, 128, 128, 2, 2, false, 32>(l, grid, s, p) ||
+         wgrad_try<float, 128, 32, 4, 1, true, 32>(l, grid, s, p) ||
+         wgrad_try<float, 128, 32, 4, 1, false, 32>(l, grid, s, p) ||
+         wgrad_try<float, 32, 128, 1, 4, true, 32>(l, grid, s, p) ||
+         wgrad_try<float, 32, 128, 1, 4, false, 32>(l, grid, s, p) ||
+         wgrad_try<float, 32, 32, 1, 1, true, 32>(l, grid, s, p) ||
+         wgrad_try<float, 32, 32, 1, 1, false, 32>(l, grid, s, p) ||
+         // f16 operands
+         wgrad_try<f16, 256, 256, 2, 4, true, 32>(l, grid, s, p) ||
+         wgrad_try<f16, 256, 256, 2, 4, true, 32, true>(l, grid, s, p) ||
+         wgrad_try<f16, 128, 128, 2, 2, true, 32>(l, grid, s, p) ||
+         wgrad_try<f16, 128, 128, 2, 2, true, 32, true>(l, grid, s, p) ||
+         wgrad_try<f16, 128, 128, 2, 2, true, 16, true>(l, grid, s, p) ||
+         wgrad_try<f16, 64, 64, 2, 2, true, 32>(l, grid, s, p) ||
+         wgrad_try<f16, 64, 64, 2, 2, true, 32, true>(l, grid, s, p) ||
+         wgrad_try<f16, 32, 32, 1, 1, true, 32>(l, grid, s, p) ||
+         wgrad_try<f16, 32, 32, 1, 1, true, 32, true>(l, grid, s, p) ||
+         wgrad_try<f16, 32, 32, 1, 1, true, 16, true>(l, grid, s, p));
+    GIF_REQUIRE(launched, "conv2d_wgrad: the route names a kernel that is not built (%s %dx%d waves %dx%d glds %d stage %d tab %d x3 %d)",
+                l.f16 ? "f16" : "f32", l.BP, l.BQ, l.WP, l.WQ, (int)l.GLDS, l.BKP, (int)l.TAB, l.X3);
+    return 0;
+}
+
+// The tiled launches of a route: the primary one and, for an f16x2 route, its guarded bf16x3 twin (a no-op unless the primary raised
+// the gate; not launched at all when the guard is switched off).  `p` carries everything but the per-launch fields.
+int wgrad_dispatch(const route::WgradRoute& r, int nsplit, hipStream_t s, WgradParams p) {
+    if (r.has_twin) {
+        const gif::H2Gate gt = gif::h2_next_gate(s);
+        if (gt.err) return gt.err;
+        p.gate = gt.word; p.gate_gen = gt.gen; p.h2_stats = gif::h2_stats_words();
+    }
+    if (int rc = wgrad_launch_one(r.primary, nsplit, s, p)) return rc;
+    if (r.has_twin && p.gate) return wgrad_launch_one(r.twin, nsplit, s, p);  // (no gate: GIF_H2_GUARD=0, unguarded)
+    return 0;
 }
 
 }  // namespace
@@ -2035,48 +2077,17 @@ int gif_pack_weight_f16(const float* w, void* wp, int R, int C, int KH, int KW, 
     return gif::check_launch("pack_weight_f16");
 }
 
-/* ---- f16 operands (BASELINE config 5): always 128x128 tiles on the LDS-DMA kernel (MFMA work on padded channels is cheap
- * at the f16 rate), fp32 partial sums, the same unpack kernel. */
-// square tile of the f16 weight-gradient kernel: 32 / 64 for the thin layers of the 512^2 / 1024^2 blocks, else 128
-static inline int wgrad_tile_f16(int Cs, int Cb) {
-    const int m = Cs > Cb ? Cs : Cb;
-    return m <= 32 ? 32 : (m <= 64 ? 64 : 128);
-}
-
-// 256 x 256 tiles on 8 waves (wave tile 128 x 64) for the f16 weight gradients with multiples of 256 channels on both sides: half
-// the LDS-DMA pieces and 6 instead of 8 operand gathers per MFMA (the 128 x 128 loop is bound by both: DESIGN 3b).  GIF_F16_WGRAD256=0: A/B.
-static inline bool wgrad_tile256_f16(const gif_conv_geom* g, bool scaled) {
-    static const int off = gif::knob("GIF_F16_WGRAD256") ? atoi(gif::knob("GIF_F16_WGRAD256")) == 0 : 0;
-    (void)scaled;  // modulated launches too (the per-sample scale table of a 32-pixel stage is 2 KB per sample)
-    return !off && g->Cs % 256 == 0 && g->Cb % 256 == 0 && (long)g->B * g->Hs * g->Ws >= 16384 && ((long)g->Hs * g->Ws) % 32 == 0;
-}
-
+/* ---- f16 operands (BASELINE config 5): square tiles on the LDS-DMA kernel (wgrad_route.h: wgrad_route_f16), fp32 partial sums, the
+ * same unpack kernel. */
 int gif_conv2d_wgrad_dims_f16(int Cs, int Cb, int* RP, int* CP) {
     GIF_REQUIRE(Cs > 0 && Cb > 0 && RP && CP, "wgrad_dims_f16: bad arguments");
-    const int t = wgrad_tile_f16(Cs, Cb);
-    *RP = (Cs + t - 1) / t * t;
-    *CP = (Cb + t - 1) / t * t;
+    route::wgrad_dims_f16(Cs, Cb, RP, CP);
     return 0;
 }
 
 int gif_conv2d_wgrad_splits_f16(const gif_conv_geom* g) {
     if (!g || g->B <= 0) return 1;
-    if (halo_wgrad_ok(g)) return halo_wgrad_splits(g);  // conv_wgrad_halo_f16: one split per persistent workgroup
-    int RP, CP;
-    gif_conv2d_wgrad_dims_f16(g->Cs, g->Cb, &RP, &CP);
-    int t = wgrad_tile_f16(g->Cs, g->Cb);
-    if (wgrad_tile256_f16(g, false)) t = 256;
-    long Ntot = (long)g->B * g->Hs * g->Ws;
-    long tiles = (long)(RP / t) * (CP / t) * g->KH * g->KW;
-    long slots = t == 256 ? 512 : t == 128 ? 1024 : 2048;  // resident workgroups: 4 per CU at 32 KB of LDS, more for the small tiles
-    long want = tiles >= slots ? 1 : slots / tiles;
-    long max_by_work = (Ntot + 4 * BKP_MAX - 1) / (4 * BKP_MAX);
-    long max_by_mem = (128L << 20) / ((long)g->KH * g->KW * RP * CP * 4);
-    long n = want;
-    if (n > max_by_work) n = max_by_work;
-    if (n > max_by_mem) n = max_by_mem;
-    if (n < 1) n = 1;
-    return (int)n;
+    return route::wgrad_splits_f16(wgrad_shape(g, false), wgrad_knobs());
 }
 
 int gif_conv2d_wgrad_f16(const void* small, const void* big, float* ws, const float* small_scale, const float* big_scale,
@@ -2087,239 +2098,111 @@ int gif_conv2d_wgrad_f16(const void* small, const void* big, float* ws, const fl
                 "conv2d_wgrad_f16: unsupported kernel/stride");
     GIF_REQUIRE((long)g->B * g->Hs * g->Ws * g->Cs < (1L << 31) && (long)g->B * g->Hb * g->Wb * g->Cb < (1L << 31),
                 "conv2d_wgrad_f16: tensors of >= 2^31 elements are not supported (32-bit offsets)");
-    WgradParams p{};
-    p.sm = small; p.bg = big; p.ws = ws; p.ss = small_scale; p.bs = big_scale;
-    p.B = g->B; p.Hs = g->Hs; p.Ws = g->Ws; p.Cs = g->Cs; p.Hb = g->Hb; p.Wb = g->Wb; p.Cb = g->Cb;
-    p.KW = g->KW; p.stride = g->stride; p.pad = g->pad; p.T = g->KH * g->KW;
-    gif_conv2d_wgrad_dims_f16(g->Cs, g->Cb, &p.RP, &p.CP);
-    const int t = wgrad_tile_f16(g->Cs, g->Cb);
-    p.Ntot = (long)g->B * g->Hs * g->Ws;
-    if (halo_wgrad_ok(g) && nsplit == halo_wgrad_splits(g) && p.RP == 32 && p.CP == 32) {
+    const bool scaled = small_scale || big_scale;
+    const route::WgradRoute r = route::wgrad_route_f16(wgrad_shape(g, scaled), nsplit, wgrad_knobs());
+    hipStream_t s = gif::as_stream(stream);
+    const int T = g->KH * g->KW;
+    const long Ntot = (long)g->B * g->Hs * g->Ws;
+    const double flops = 2.0 * Ntot * (double)g->Cs * g->Cb * T;
+    const void* zero = gif::zero_page16();
+    GIF_REQUIRE(zero, "conv2d_wgrad_f16: zero page lookup failed");
+    if (r.primary.kernel == route::WGRAD_HALO) {
         HaloWgradParams q{};
         q.sm = small; q.bg = big; q.ws = ws; q.ss = small_scale; q.bs = big_scale;
         q.B = g->B; q.Hs = g->Hs; q.Ws = g->Ws; q.Hb = g->Hb; q.Wb = g->Wb; q.Cs = g->Cs; q.Cb = g->Cb;
         q.KH = g->KH; q.KW = g->KW; q.pad = g->pad;
         q.tiles_x = gif::cdiv(g->Ws, 16); q.tiles_y = gif::cdiv(g->Hs, 16); q.ntiles = g->B * q.tiles_x * q.tiles_y;
-        q.zero = gif::zero_page16();
-        GIF_REQUIRE(q.zero, "conv2d_wgrad_f16: zero page lookup failed");
-        hipStream_t hs = gif::as_stream(stream);
-        gif::ProfScope prof(7, 2.0 * p.Ntot * (double)g->Cs * g->Cb * p.T, hs, (int)p.Ntot, g->Cs, g->Cb,
-                            p.T * 10 + g->stride + (small_scale || big_scale ? 100 : 0));
+        q.zero = zero;
+        gif::ProfScope prof(r.family, flops, s, (int)Ntot, g->Cs, g->Cb, T * 10 + g->stride + (scaled ? 100 : 0));
         const size_t lds = (size_t)2 * kHwBufHalfs * sizeof(gif::f16);
-        static gif::LdsAttr attr;
-        static const int tr_off = gif::knob("GIF_F16_HALO_WGRAD_TR") ? atoi(gif::knob("GIF_F16_HALO_WGRAD_TR")) == 0 : 0;  // A/B knob
-        if (tr_off) {
+        const dim3 grid((unsigned)(r.primary.wgs_per_split * nsplit));
+        if (!r.primary.TR) {
+            static gif::LdsAttr attr;
             attr.ensure(reinterpret_cast<const void*>(conv_wgrad_halo_f16<false>), lds);
-            hipLaunchKernelGGL(conv_wgrad_halo_f16<false>, dim3((unsigned)nsplit), dim3(256), lds, hs, q);
+            hipLaunchKernelGGL(conv_wgrad_halo_f16<false>, grid, dim3(r.primary.threads), lds, s, q);
         } else {
             static gif::LdsAttr attr_tr;
             attr_tr.ensure(reinterpret_cast<const void*>(conv_wgrad_halo_f16<true>), lds);
-            hipLaunchKernelGGL(conv_wgrad_halo_f16<true>, dim3((unsigned)nsplit), dim3(256), lds, hs, q);
+            hipLaunchKernelGGL(conv_wgrad_halo_f16<true>, grid, dim3(r.primary.threads), lds, s, q);
         }
         return gif::check_launch("conv2d_wgrad_f16(halo)");
     }
-    long chunk = (p.Ntot + nsplit - 1) / nsplit;
-    p.chunk = (chunk + BKP_MAX - 1) / BKP_MAX * BKP_MAX;
-    if (p.chunk < BKP_MAX) p.chunk = BKP_MAX;
-    const bool scaled = small_scale || big_scale;
-    const long HWs = (long)g->Hs * g->Ws;
-    const bool st16 = scaled && HWs % 32 != 0;  // modulated layer on 4x4 maps: 16-pixel stages
-    // the 64-wide tile has no 16-pixel-stage variant (one DMA pass covers 32 pixel rows): such a launch runs 32x32 tiles over
-    // the same 64-padded workspace
-    const int tl = (t == 64 && st16) ? 32 : t;
-    p.tiles_q = p.CP / tl;
-    p.tiles_pq = (p.RP / tl) * p.tiles_q;
-    dim3 grid((unsigned)(p.tiles_pq * p.T * nsplit));
-    hipStream_t s = gif::as_stream(stream);
-    p.zero = gif::zero_page16();
-    GIF_REQUIRE(p.zero, "conv2d_wgrad_f16: zero page lookup failed");
-    double flops = 2.0 * p.Ntot * (double)g->Cs * g->Cb * p.T;
-    gif::ProfScope prof(7, flops, s, (int)p.Ntot, g->Cs, g->Cb, p.T * 10 + g->stride + (small_scale || big_scale ? 100 : 0));
-    p.stab_nb = (int)((p.chunk + HWs - 1) / HWs + 1);
-    if (p.stab_nb > g->B) p.stab_nb = g->B;
+    WgradParams p{};
+    p.sm = small; p.bg = big; p.ws = ws; p.ss = small_scale; p.bs = big_scale;
+    p.B = g->B; p.Hs = g->Hs; p.Ws = g->Ws; p.Cs = g->Cs; p.Hb = g->Hb; p.Wb = g->Wb; p.Cb = g->Cb;
+    p.KW = g->KW; p.stride = g->stride; p.pad = g->pad; p.T = T;
+    p.RP = r.RP; p.CP = r.CP; p.Ntot = Ntot; p.chunk = r.chunk;
+    p.tiles_q = r.tiles_q; p.tiles_pq = r.tiles_pq; p.stab_nb = r.stab_nb; p.zero = zero;
+    gif::ProfScope prof(r.family, flops, s, (int)Ntot, g->Cs, g->Cb, T * 10 + g->stride + (scaled ? 100 : 0));
     if (scaled) {
         // the scale table is indexed per stage: a stage must not straddle two samples
-        GIF_REQUIRE((size_t)p.stab_nb * 2 * tl * sizeof(float) <= 64 * 1024, "conv2d_wgrad_f16: scale table too large");
+        const long HWs = (long)g->Hs * g->Ws;
+        GIF_REQUIRE((size_t)r.stab_nb * 2 * r.tile_f16 * sizeof(float) <= 64 * 1024, "conv2d_wgrad_f16: scale table too large");
         GIF_REQUIRE(HWs % 16 == 0, "conv2d_wgrad_f16: modulated weight gradient needs Hs*Ws %% 16 == 0 (got %ld)", HWs);
     }
-    if (tl == 128 && wgrad_tile256_f16(g, scaled) && (!scaled || (size_t)p.stab_nb * 512 * sizeof(float) <= 32 * 1024)) {
-        p.tiles_q = p.CP / 256;
-        p.tiles_pq = (p.RP / 256) * p.tiles_q;
-        const dim3 g256((unsigned)(p.tiles_pq * p.T * nsplit));
-        if (!scaled) wgrad_launch<gif::f16, 256, 256, 2, 4, true, 32>(g256, 512, s, p);
-        else wgrad_launch<gif::f16, 256, 256, 2, 4, true, 32, true>(g256, 512, s, p);
-    } else if (tl == 128) {
-        if (!scaled) wgrad_launch<gif::f16, 128, 128, 2, 2, true, 32>(grid, 256, s, p);
-        else if (!st16) wgrad_launch<gif::f16, 128, 128, 2, 2, true, 32, true>(grid, 256, s, p);
-        else wgrad_launch<gif::f16, 128, 128, 2, 2, true, 16, true>(grid, 256, s, p);
-    } else if (tl == 64) {
-        if (!scaled) wgrad_launch<gif::f16, 64, 64, 2, 2, true, 32>(grid, 256, s, p);
-        else wgrad_launch<gif::f16, 64, 64, 2, 2, true, 32, true>(grid, 256, s, p);
-    } else {
-        if (!scaled) wgrad_launch<gif::f16, 32, 32, 1, 1, true, 32>(grid, 64, s, p);
-        else if (!st16) wgrad_launch<gif::f16, 32, 32, 1, 1, true, 32, true>(grid, 64, s, p);
-        else wgrad_launch<gif::f16, 32, 32, 1, 1, true, 16, true>(grid, 64, s, p);
-    }
+    if (int rc = wgrad_dispatch(r, nsplit, s, p)) return rc;
     return gif::check_launch("conv2d_wgrad_f16");
 }
 
 int gif_conv2d_wgrad_dims(int Cs, int Cb, int* RP, int* CP) {
     GIF_REQUIRE(Cs > 0 && Cb > 0 && RP && CP, "wgrad_dims: bad arguments");
-    wgrad_dims(Cs, Cb, RP, CP);
+    route::wgrad_dims(Cs, Cb, RP, CP);
     return 0;
 }
 
+// The count follows the kernel a later call is expected to launch under the PROCESS's contraction mode (wgrad_tiles_per_split takes the
+// mode as a parameter: a caller that knows the mode of the call it sizes can be given a way to say so).
 int gif_conv2d_wgrad_splits(const gif_conv_geom* g) {
     if (!g || g->B <= 0) return 1;
-    if (small_wgrad_ok(g, false)) return 256;  // one 16-wave workgroup per CU (conv_wgrad_small_mfma); scaled calls never
-                                               // reach that kernel and simply use 256 splits of the generic one
-    int RP, CP;
-    wgrad_dims(g->Cs, g->Cb, &RP, &CP);
-    // (scaled launches of the same geometry use 128-row tiles: they simply get half the splits they could use)
-    long Ntot = (long)g->B * g->Hs * g->Ws;
-    long tiles = (long)(RP / tile_rows(g->Cs, g->Cb, false, Ntot)) * (CP / tile_of(g->Cb)) * g->KH * g->KW;
-    if (tile_of(g->Cs) == 128 && tile_of(g->Cb) == 32 && g->KH * g->KW > 1 && thin_taps_on() && h2v2_on() &&
-        gif::fp32_mfma_mode() == GIF_FP32_MFMA_F16X2) {
-        // thin big side: the f16x2 kernel (conv_wgrad_h2v2<false, true>, the only one that groups taps — the condition mirrors the
-        // `h2 && x3_thin && thin_taps_on() && h2v2_on()` of conv2d_wgrad_f32_impl under the process's contraction mode) puts several taps
-        // into one column tile: fewer, larger workgroups per split.  The native / bf16x3 kernels run one workgroup per tap and keep
-        // their own count (advisor, round 5: they got ~4.5 x the splits, i.e. workspace and unpack traffic, for nothing)
-        int tpt, tg;
-        thin_tap_tiles(g->Cb, g->KH * g->KW, &tpt, &tg);
-        tiles = (long)(RP / 128) * tg;
-    }
+    const route::WgradShape sh = wgrad_shape(g, false);
+    const route::WgradKnobs k = wgrad_knobs();
+    const int mode = gif::fp32_mfma_mode();
 #ifdef GIF_WGRAD_KX3_PROBE  // (timing probe: a third of the tap groups per split -> three times the splits)
-    else if (g->KH * g->KW == 9 && gif::fp32_mfma_mode() == GIF_FP32_MFMA_F16X2) tiles /= 3;
+    if (!route::small_wgrad_ok(sh, k.small_wgrad) && !route::thin_taps_shape(sh, mode, k) && g->KH * g->KW == 9 && mode == GIF_FP32_MFMA_F16X2) {
+        int RP, CP;
+        route::wgrad_dims(g->Cs, g->Cb, &RP, &CP);
+        return route::wgrad_clamp_splits(route::wgrad_tiles_per_split(sh, mode, k) / 3, 1024, route::wgrad_ntot(sh), 9L * RP * CP * 4);
+    }
 #endif
-    // 2 workgroups fit per CU (64 KB LDS each) => 512 concurrent slots on 256 CUs: fill k full rounds of 512
-    // and never spill a few blocks into an extra, almost empty round (floor, not ceil)
-    long want = tiles >= 1024 ? 1 : 1024 / tiles;
-    long max_by_work = (Ntot + 4 * BKP_MAX - 1) / (4 * BKP_MAX);  // >= 4 stages per split
-    long bytes_per_split = (long)g->KH * g->KW * RP * CP * 4;
-    long max_by_mem = (128L << 20) / bytes_per_split;
-    long n = want;
-    if (n > max_by_work) n = max_by_work;
-    if (n > max_by_mem) n = max_by_mem;
-    if (n < 1) n = 1;
-    return (int)n;
+    return route::wgrad_splits(sh, mode, k);
 }
 
-// x3: 0 native fp32 MFMA, 1 bf16x3, 2 f16x2 with the guarded bf16x3 fallback (launch shapes f16x2 is not built for run bf16x3)
+// mode: 0 native fp32 MFMA, 1 bf16x3, 2 f16x2 with the guarded bf16x3 fallback (launch shapes f16x2 is not built for run bf16x3)
 static int conv2d_wgrad_f32_impl(const float* small, const float* big, float* ws, const float* small_scale,
-                                 const float* big_scale, const gif_conv_geom* g, int nsplit, gif_stream_t stream, int x3_mode) {
-    bool x3 = x3_mode != 0;
+                                 const float* big_scale, const gif_conv_geom* g, int nsplit, gif_stream_t stream, int mode) {
     GIF_REQUIRE(g && small && big && ws && nsplit >= 1, "conv2d_wgrad: bad arguments");
     GIF_REQUIRE(g->Cb % 4 == 0 && g->Cs % 4 == 0, "conv2d_wgrad: channels must be multiples of 4");
     GIF_REQUIRE(g->KH >= 1 && g->KH <= 3 && g->KW >= 1 && g->KW <= 3 && (g->stride == 1 || g->stride == 2),
                 "conv2d_wgrad: unsupported kernel/stride");
     GIF_REQUIRE((long)g->B * g->Hs * g->Ws * g->Cs < (1L << 31) && (long)g->B * g->Hb * g->Wb * g->Cb < (1L << 31),
                 "conv2d_wgrad: tensors of >= 2^31 elements are not supported (32-bit offsets)");
-    WgradParams p{};
-    p.sm = small; p.bg = big; p.ws = ws; p.ss = small_scale; p.bs = big_scale;
-    p.B = g->B; p.Hs = g->Hs; p.Ws = g->Ws; p.Cs = g->Cs; p.Hb = g->Hb; p.Wb = g->Wb; p.Cb = g->Cb;
-    p.KW = g->KW; p.stride = g->stride; p.pad = g->pad; p.T = g->KH * g->KW;
-    wgrad_dims(g->Cs, g->Cb, &p.RP, &p.CP);
-    p.Ntot = (long)g->B * g->Hs * g->Ws;
-    long chunk = (p.Ntot + nsplit - 1) / nsplit;
-    p.chunk = (chunk + BKP_MAX - 1) / BKP_MAX * BKP_MAX;
-    if (p.chunk < BKP_MAX) p.chunk = BKP_MAX;
-    const int bp = tile_of(g->Cs), bq = tile_of(g->Cb);
-    // bf16x3: 128x128 tiles only (the 256x128 tile's 128 accumulator registers leave no room for the split operands); layers
-    // with a <= 32-channel side stay on the native kernels (same operands, same workspace)
-    const long HWs = (long)g->Hs * g->Ws;
-    p.stab_nb = (int)((p.chunk + HWs - 1) / HWs + 1);
-    if (p.stab_nb > g->B) p.stab_nb = g->B;
-    const bool tab_fits = HWs % 16 == 0 && (size_t)p.stab_nb * 256 * sizeof(float) <= 64 * 1024;
-    // bf16x3 tiles: 128x128, and 128x32 for the un-modulated layers with a thin big side (the 24-channel condition-noise maps)
-    static const int x3_thin_off = gif::knob("GIF_X3_WGRAD_THIN") ? atoi(gif::knob("GIF_X3_WGRAD_THIN")) == 0 : 0;
-    const bool x3_thin = x3 && !x3_thin_off && tile_of(g->Cs) == 128 && tile_of(g->Cb) == 32 && !small_scale && !big_scale;
-    x3 = x3 && tile_of(g->Cs) == 128 && (tile_of(g->Cb) == 128 || x3_thin) && (!(small_scale || big_scale) || tab_fits);
-    const bool big_tile = !x3 && wgrad_big_tile(g->Cs, g->Cb, small_scale || big_scale, p.Ntot) && !gif::knob("GIF_CONV_VARIANT");
-    p.tiles_q = p.CP / bq;
-    p.tiles_pq = (p.RP / (big_tile ? 256 : bp)) * p.tiles_q;
-    dim3 grid((unsigned)(p.tiles_pq * p.T * nsplit));
+    const bool scaled = small_scale || big_scale;
+    const route::WgradRoute r = route::wgrad_route(wgrad_shape(g, scaled), mode, nsplit, wgrad_knobs());
     hipStream_t s = gif::as_stream(stream);
-    p.zero = gif::zero_page16();
-    GIF_REQUIRE(p.zero, "conv2d_wgrad: zero page lookup failed");
-    double flops = 2.0 * p.Ntot * (double)g->Cs * g->Cb * p.T;
-    if (small_wgrad_ok(g, small_scale || big_scale)) {
-        gif::ProfScope prof(1, flops, s, (int)p.Ntot, g->Cs, g->Cb, p.T * 10 + g->stride);
+    const int T = g->KH * g->KW;
+    const long Ntot = (long)g->B * g->Hs * g->Ws;
+    const double flops = 2.0 * Ntot * (double)g->Cs * g->Cb * T;
+    const void* zero = gif::zero_page16();
+    GIF_REQUIRE(zero, "conv2d_wgrad: zero page lookup failed");
+    gif::ProfScope prof(r.family, flops, s, (int)Ntot, g->Cs, g->Cb, T * 10 + g->stride + (scaled ? 100 : 0));
+    if (r.primary.kernel == route::WGRAD_SMALL) {
         SmallWgradParams q{};
         q.sm = small; q.bg = big; q.ws = ws;
-        q.B = g->B; q.H = g->Hs; q.W = g->Ws; q.Cs = g->Cs; q.Cb = g->Cb; q.RP = p.RP; q.CP = p.CP;
-        q.Ntot = p.Ntot;
-        long ch = (p.Ntot + nsplit - 1) / nsplit;
-        q.chunk = (ch + 63) / 64 * 64;
+        q.B = g->B; q.H = g->Hs; q.W = g->Ws; q.Cs = g->Cs; q.Cb = g->Cb; q.RP = r.RP; q.CP = r.CP;
+        q.Ntot = Ntot; q.chunk = r.chunk;
         const size_t lds = (size_t)8 * 18 * 256 * sizeof(float);
         static gif::LdsAttr attr;
         attr.ensure(reinterpret_cast<const void*>(conv_wgrad_small_mfma), lds);
-        hipLaunchKernelGGL(conv_wgrad_small_mfma, dim3((unsigned)nsplit), dim3(1024), lds, s, q);
+        hipLaunchKernelGGL(conv_wgrad_small_mfma, dim3((unsigned)(r.primary.wgs_per_split * nsplit)), dim3(r.primary.threads), lds, s, q);
         return gif::check_launch("conv2d_wgrad(small)");
     }
-    {
-        static const int x3_simple_p = gif::knob("GIF_X3_WGRAD_SIMPLE") ? atoi(gif::knob("GIF_X3_WGRAD_SIMPLE")) : 0;
-        const bool tab_p = (small_scale || big_scale) && tab_fits;
-        const bool h2_p = x3 && x3_mode == 2 && !x3_simple_p && (x3_thin || !tab_p || HWs % 32 == 0);  // (the same condition as below)
-        gif::ProfScope prof(h2_p ? 15 : x3 ? 9 : 1, flops, s, (int)p.Ntot, g->Cs, g->Cb, p.T * 10 + g->stride + (small_scale || big_scale ? 100 : 0));
-        const char* env = gif::knob("GIF_CONV_VARIANT");
-        const int variant = env ? atoi(env) : 0;
-        const bool glds = !small_scale && !big_scale && variant != 1;
-#define GIF_WGRAD_LAUNCH(BP_, BQ_, WP_, WQ_, TH_)                                                                  \
-    if (glds) wgrad_launch<float, BP_, BQ_, WP_, WQ_, true, 32>(grid, TH_, s, p);                                        \
-    else wgrad_launch<float, BP_, BQ_, WP_, WQ_, false, 32>(grid, TH_, s, p)
-        // Un-modulated f16x2 launches run the scale-table instantiation with unit scales (x 1.0f: bit-identical results) wherever it
-        // applies: that instantiation's instruction stream is 3-5 % faster than the plain one on every 128 x 128-tile shape — 3.02 -> 2.91 ms
-        // at 128@256^2, 2.92 -> 2.77 at 512@64^2, the modulated launches themselves 2.82 / 2.79 — for no reason visible in the source (the
-        // extra multiply moves hipcc's interleave of the conversion); -0.6 ms per step, three alternating pairs.  GIF_H2_WGRAD_PLAIN_TAB=0: A/B
-        static const int force_tab = gif::knob("GIF_H2_WGRAD_PLAIN_TAB") ? atoi(gif::knob("GIF_H2_WGRAD_PLAIN_TAB")) != 0 : 1;
-        const bool tab = ((small_scale || big_scale) || (force_tab && x3 && x3_mode == 2 && HWs % 32 == 0)) && (variant != 1 || x3) && tab_fits;
-        static const int x3_simple = gif::knob("GIF_X3_WGRAD_SIMPLE") ? atoi(gif::knob("GIF_X3_WGRAD_SIMPLE")) : 0;  // A/B: 16-pixel stages, no pipeline
-        // f16x2: the software-pipelined 32-pixel-stage instantiations; the launch is followed by its guarded bf16x3 twin
-        const bool h2 = x3 && x3_mode == 2 && !x3_simple && (x3_thin || !tab || HWs % 32 == 0);
-        if (h2) {
-            const gif::H2Gate gt = gif::h2_next_gate(s);
-            if (gt.err) return gt.err;
-            p.gate = gt.word; p.gate_gen = gt.gen; p.h2_stats = gif::h2_stats_words();
-            if (x3_thin && thin_taps_on() && p.T > 1 && h2v2_on()) {
-                // several taps per 128-column tile (conv_wgrad_h2v2<false, true>); the guarded twin below keeps its per-tap grid
-                WgradParams q = p;
-                thin_tap_tiles(g->Cb, p.T, &q.tpt, &q.tgroups);
-                wgrad_launch_v2(false, dim3((unsigned)(p.tiles_pq * q.tgroups * nsplit)), s, q, true);
-            } else if (x3_thin) wgrad_launch<float, 128, 32, 2, 1, true, 32, false, 2>(grid, 128, s, p);
-            else if (h2v2_on()) wgrad_launch_v2(tab, grid, s, p);
-            else if (tab) wgrad_launch<float, 128, 128, 2, 2, true, 32, true, 2>(grid, 256, s, p);
-            else wgrad_launch<float, 128, 128, 2, 2, true, 32, false, 2>(grid, 256, s, p);
-        }
-        if (h2 && !p.gate) {
-            // unguarded (GIF_H2_GUARD=0): done
-        } else if (x3_thin) {
-            // two waves of 64x32: 3 fragment splits per 12 MFMAs (four waves of 32x32: 2 per 6 — GIF_X3_WGRAD_THIN=4 for the A/B:
-            // 128x24 at 256^2 76 -> 80 TFLOP/s, 256x24 at 128^2 70 -> 78, 512x24 at 64^2 80 -> 82)
-            static const int thin4 = gif::knob("GIF_X3_WGRAD_THIN") ? atoi(gif::knob("GIF_X3_WGRAD_THIN")) == 4 : 0;
-            if (thin4) wgrad_launch<float, 128, 32, 4, 1, true, 32, false, 1>(grid, 256, s, p);
-            else wgrad_launch<float, 128, 32, 2, 1, true, 32, false, 1>(grid, 128, s, p);
-        } else if (x3 && tab && HWs % 32 == 0 && !x3_simple) {
-            wgrad_launch<float, 128, 128, 2, 2, true, 32, true, 1>(grid, 256, s, p);
-        } else if (x3 && tab) {
-            wgrad_launch<float, 128, 128, 2, 2, true, 16, true, 1>(grid, 256, s, p);
-        } else if (x3 && !x3_simple) {
-            wgrad_launch<float, 128, 128, 2, 2, true, 32, false, 1>(grid, 256, s, p);
-        } else if (x3) {
-            wgrad_launch<float, 128, 128, 2, 2, true, 16, false, 1>(grid, 256, s, p);
-        } else if (big_tile) {
-            wgrad_launch<float, 256, 128, 2, 2, true, 16>(grid, 256, s, p);
-        } else if (bp == 128 && bq == 128 && tab) {
-            // modulated wgrad (x*s, dy*d): LDS-DMA operands + scale table
-            wgrad_launch<float, 128, 128, 2, 2, true, 16, true>(grid, 256, s, p);
-        } else if (bp == 128 && bq == 128 && glds && variant != 7) {
-            // 16-pixel stages: 32 KB of LDS per workgroup => 4 workgroups (16 waves) per CU; +6 % over 32-pixel stages
-            wgrad_launch<float, 128, 128, 2, 2, true, 16>(grid, 256, s, p);
-        } else if (bp == 128 && bq == 128) { GIF_WGRAD_LAUNCH(128, 128, 2, 2, 256); }
-        else if (bp == 128 && bq == 32) { GIF_WGRAD_LAUNCH(128, 32, 4, 1, 256); }
-        else if (bp == 32 && bq == 128) { GIF_WGRAD_LAUNCH(32, 128, 1, 4, 256); }
-        else { GIF_WGRAD_LAUNCH(32, 32, 1, 1, 64); }
-#undef GIF_WGRAD_LAUNCH
-    }
+    WgradParams p{};
+    p.sm = small; p.bg = big; p.ws = ws; p.ss = small_scale; p.bs = big_scale;
+    p.B = g->B; p.Hs = g->Hs; p.Ws = g->Ws; p.Cs = g->Cs; p.Hb = g->Hb; p.Wb = g->Wb; p.Cb = g->Cb;
+    p.KW = g->KW; p.stride = g->stride; p.pad = g->pad; p.T = T;
+    p.RP = r.RP; p.CP = r.CP; p.Ntot = Ntot; p.chunk = r.chunk;
+    p.tiles_q = r.tiles_q; p.tiles_pq = r.tiles_pq; p.stab_nb = r.stab_nb; p.zero = zero;
+    if (int rc = wgrad_dispatch(r, nsplit, s, p)) return rc;
     return gif::check_launch("conv2d_wgrad");
 }
 
@@ -2353,24 +2236,13 @@ int gif_unpack_wgrad_f32(const float* ws, float* dw, int nsplit, int R, int C, i
  * conv_wgrad_mfma in "planes" mode), then dW = A'^T dU A' in the unpack kernel: 16 instead of 36 multiplies per tile. */
 int gif_conv3x3_winograd_wgrad_splits(int B, int H, int W, int Cs, int Cb) {
     if (B <= 0 || H <= 0 || W <= 0 || Cs <= 0 || Cb <= 0) return 1;
-    int RP, CP;
-    wgrad_dims(Cs, Cb, &RP, &CP);
-    long Ntot = (long)B * (H / 2) * (W / 2);
-    long tiles = (long)(RP / tile_rows(Cs, Cb, false, Ntot)) * (CP / tile_of(Cb)) * 16;
-    long want = tiles >= 1024 ? 1 : 1024 / tiles;
-    long max_by_work = (Ntot + 4 * BKP_MAX - 1) / (4 * BKP_MAX);
-    long max_by_mem = (128L << 20) / (16L * RP * CP * 4);
-    long n = want;
-    if (n > max_by_work) n = max_by_work;
-    if (n > max_by_mem) n = max_by_mem;
-    if (n < 1) n = 1;
-    return (int)n;
+    const route::WgradShape planes{B, H / 2, W / 2, Cb, H / 2, W / 2, Cs, 1, 1, 1, 0, false, true};
+    return route::wgrad_splits(planes, gif::fp32_mfma_mode(), wgrad_knobs());  // (the plane GEMMs' count does not depend on the mode)
 }
 
 static int conv3x3_winograd_wgrad_impl(const float* x, const float* gy, float* V, float* Mg, float* ws,
                                        const float* small_scale, const float* big_scale, int B, int H, int W, int Cs, int Cb,
-                                       int nsplit, gif_stream_t stream, int x3_mode) {
-    bool x3 = x3_mode != 0;
+                                       int nsplit, gif_stream_t stream, int mode) {
     GIF_REQUIRE(gy && V && Mg && ws && nsplit >= 1, "winograd_wgrad: bad arguments");  // x == NULL: V is already filled
     GIF_REQUIRE(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "winograd_wgrad: bad dims (H, W must be even)");
     GIF_REQUIRE(Cs > 0 && Cb > 0 && Cs % 4 == 0 && Cb % 4 == 0, "winograd_wgrad: channels must be multiples of 4");
@@ -2389,52 +2261,21 @@ static int conv3x3_winograd_wgrad_impl(const float* x, const float* gy, float* V
             if (int rc = gif::winograd_input_transform(x, big_scale, V, B, H, W, Cb, s)) return rc;
         if (int rc = gif::winograd_gy_transform(gy, small_scale, Mg, B, H, W, Cs, s)) return rc;
     }
-    x3 = x3 && tile_of(CsP) == 128 && tile_of(CbP) == 128;
-    static const int x3_simple_p = gif::knob("GIF_X3_WGRAD_SIMPLE") ? atoi(gif::knob("GIF_X3_WGRAD_SIMPLE")) : 0;
-    gif::ProfScope prof((x3 && x3_mode == 2 && !x3_simple_p) ? 16 : x3 ? 11 : 3, flops, s, (int)((long)B * H * W), Cs, Cb,
-                        1091 + (small_scale || big_scale ? 100 : 0));
+    // one "image" of 1 x ntiles pixels per plane, 1x1 taps; the transforms have applied the per-sample scales
+    const route::WgradShape planes{1, 1, (int)ntiles, CbP, 1, (int)ntiles, CsP, 1, 1, 1, 0, false, true};
+    const route::WgradRoute r = route::wgrad_route(planes, mode, nsplit, wgrad_knobs());
+    gif::ProfScope prof(r.family, flops, s, (int)((long)B * H * W), Cs, Cb, 1091 + (small_scale || big_scale ? 100 : 0));
     WgradParams p{};
     p.sm = Mg; p.bg = V; p.ws = ws; p.ss = nullptr; p.bs = nullptr;
-    // one "image" of 1 x ntiles pixels per plane, 1x1 taps
     p.B = 1; p.Hs = 1; p.Ws = (int)ntiles; p.Cs = CsP; p.Hb = 1; p.Wb = (int)ntiles; p.Cb = CbP;
     p.KW = 1; p.stride = 1; p.pad = 0; p.T = 16;
     p.sm_plane = ntiles_pad * CsP;
     p.bg_plane = ntiles_pad * CbP;
-    wgrad_dims(CsP, CbP, &p.RP, &p.CP);
-    p.Ntot = ntiles;
-    long chunk = (p.Ntot + nsplit - 1) / nsplit;
-    p.chunk = (chunk + BKP_MAX - 1) / BKP_MAX * BKP_MAX;
-    if (p.chunk < BKP_MAX) p.chunk = BKP_MAX;
-    const int bp = tile_of(CsP), bq = tile_of(CbP);
-    const bool big = !x3 && wgrad_big_tile(CsP, CbP, false, ntiles);
-    p.tiles_q = p.CP / bq;
-    p.tiles_pq = (p.RP / (big ? 256 : bp)) * p.tiles_q;
-    dim3 grid((unsigned)(p.tiles_pq * p.T * nsplit));
+    p.RP = r.RP; p.CP = r.CP; p.Ntot = ntiles; p.chunk = r.chunk;
+    p.tiles_q = r.tiles_q; p.tiles_pq = r.tiles_pq; p.stab_nb = r.stab_nb;
     p.zero = gif::zero_page16();
     GIF_REQUIRE(p.zero, "winograd_wgrad: zero page lookup failed");
-    static const int x3_simple = gif::knob("GIF_X3_WGRAD_SIMPLE") ? atoi(gif::knob("GIF_X3_WGRAD_SIMPLE")) : 0;
-    const bool h2 = x3 && x3_mode == 2 && !x3_simple;
-    if (h2) {
-        const gif::H2Gate gt = gif::h2_next_gate(s);
-        if (gt.err) return gt.err;
-        p.gate = gt.word; p.gate_gen = gt.gen; p.h2_stats = gif::h2_stats_words();
-        if (h2v2_on()) {
-            // the plane GEMMs too run the scale-table instantiation with a one-row table of ones (see conv2d_wgrad_f32_impl: 3-5 % faster)
-            static const int plain_tab = gif::knob("GIF_H2_WGRAD_PLAIN_TAB") ? atoi(gif::knob("GIF_H2_WGRAD_PLAIN_TAB")) != 0 : 1;
-            WgradParams q = p;
-            q.stab_nb = 1;
-            wgrad_launch_v2(plain_tab != 0, grid, s, plain_tab ? q : p);
-        }
-        else wgrad_launch<float, 128, 128, 2, 2, true, 32, false, 2>(grid, 256, s, p);
-    }
-    if (h2 && !p.gate) {}
-    else if (x3 && !x3_simple) wgrad_launch<float, 128, 128, 2, 2, true, 32, false, 1>(grid, 256, s, p);
-    else if (x3) wgrad_launch<float, 128, 128, 2, 2, true, 16, false, 1>(grid, 256, s, p);
-    else if (big) wgrad_launch<float, 256, 128, 2, 2, true, 16>(grid, 256, s, p);
-    else if (bp == 128 && bq == 128) wgrad_launch<float, 128, 128, 2, 2, true, 16>(grid, 256, s, p);
-    else if (bp == 128 && bq == 32) wgrad_launch<float, 128, 32, 4, 1, true, 32>(grid, 256, s, p);
-    else if (bp == 32 && bq == 128) wgrad_launch<float, 32, 128, 1, 4, true, 32>(grid, 256, s, p);
-    else wgrad_launch<float, 32, 32, 1, 1, true, 32>(grid, 64, s, p);
+    if (int rc = wgrad_dispatch(r, nsplit, s, p)) return rc;
     return gif::check_launch("conv3x3_winograd_wgrad");
 }
 

@@ -2,7 +2,7 @@
 
 The rest of the suite picks its shapes by model layer.  Here each row of the tables is a shape computed from a dispatch predicate
 (gif_amd/ops.py: winograd_eligible, x3_conv, x3_tapdense, h2_conv; csrc/conv_igemm.hip: launch(), run_phases, rows_thin_ok,
-halo_eligible; csrc/conv_wgrad.hip: small_wgrad_ok, wgrad_big_tile, the x3 / x3_thin tile rules; csrc/elementwise.hip:
+halo_eligible; csrc/wgrad_route.h: small_wgrad_ok, wgrad_big_tile, the x3 / x3_thin tile rules of wgrad_route; csrc/elementwise.hip:
 upfirdn2d_impl, gif::reduce_partials): the last shape that takes a route and the first that does not.  Each row's comment names the
 predicate and the side.
 
@@ -29,7 +29,8 @@ Every case prints its ratio ("[route ratio]" lines with -s) so that a re-measure
 Route assertions, where the library exposes them: ops.prof_read(family) (one record per OP in the family the op ran in: it proves the
 kernel family and contraction mode, not the tile size), ops.prof_winograd_calls(), gif_conv2d_f16_halo_eligible and
 gif_conv2d_x3_eligible.  Tile sizes, the bulk + remainder split and the merged transposed phases are not observable from Python:
-there the row comment is the claim (confirmed by a kernel trace of this module when the tables change)."""
+there the row comment is the claim (confirmed by a kernel trace of this module when the tables change).  For the weight gradient the
+claim is checked on the CPU: csrc/wgrad_route.h returns the whole route as a value, tests/test_wgrad_route.py holds its table."""
 import math
 import zlib
 from typing import NamedTuple, Optional
@@ -181,8 +182,8 @@ ROWS = [
     Row("c17_o33_s2", "fwd", (3, 17, 33, 3, 2, 0, 17, 23), DENSE),  # 17 -> 20 active, cout_act 36 > 32: a strided FORWARD conv stays dense
     Row("c33_o17_1x1_s2", "fwd", (2, 33, 17, 1, 2, 0, 31, 19), DIRECT, "full"),
     Row("c33_o9_dgrad_1x1_s2", "dgrad", (2, 9, 33, 1, 2, 0, 31, 19), DIRECT),   # 1x1 stride 2: three empty phases (zero-filled)
-    # ---- weight gradient (conv_wgrad.hip): bf16x3 / f16x2 need tile_of(Cs) == 128 and tile_of(Cb) == 128 or x3_thin (Cb <= 32,
-    # unscaled); small_wgrad_ok: 3x3 s1 p1, Cs <= 32, Cb <= 16, B*H*W >= 65536; wgrad_big_tile: Ntot >= 16384, RP % 256 == 0
+    # ---- weight gradient (csrc/wgrad_route.h, wgrad_route): bf16x3 / f16x2 need tile_of(Cs) == 128 and tile_of(Cb) == 128 or x3_thin
+    # (Cb <= 32, unscaled); small_wgrad_ok: 3x3 s1 p1, Cs <= 32, Cb <= 16, B*H*W >= 65536; wgrad_big_tile: Ntot >= 16384, RP % 256 == 0
     Row("wg_x3_thin", "wgrad", (2, 24, 48, 3, 1, 1, 33, 35), WGRAD),             # Cs 48 (128), Cb 24 (32) -> x3_thin
     Row("wg_x3", "wgrad", (2, 36, 40, 3, 2, 0, 33, 35), WGRAD),                  # both > 32 -> 128x128 bf16x3 / f16x2
     Row("wg_both_thin", "wgrad", (2, 24, 20, 3, 1, 1, 33, 35), WGRAD_NATIVE),    # Cs 20 <= 32 -> native kernel in every mode
