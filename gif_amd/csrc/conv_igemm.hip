@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_route.h"
 
 #ifdef GIF_X3_TIMING_PROBE
 // tools/probes/x3_sync_probe.sh: cycles the waves of the bf16x3 direct kernel spend at the mid-stage sync (own DMA wait, barrier), cycles in the K loop, waves
@@ -101,11 +102,6 @@ struct GatherParams {
     int t2_tx, t2_ty;          // halo kernel: 16 x 16-pixel patches per row / column of the output sub-grid
     int halo_dbg;              // halo kernel: ablation bits of the probe (GIF_HALO_DBG; results are wrong when set)
 };
-
-// partial-sum rows handed out to the launches of one op (bulk + remainder launches, transposed-conv phases), and the tile height
-// of the last launch (host side, per calling thread)
-thread_local int t_part_rows = 0;
-thread_local int t_last_bm = 0;
 
 // XCD-aware, bijective block remap (cdna guide T1): consecutive logical tiles share an XCD's L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
@@ -1743,387 +1739,192 @@ __global__ void __launch_bounds__(256, 3) conv_halo_f16(const GatherParams p) {
     conv_epilogue<BM, BN, 8, MT, NT, T, 256, true, halo_lds_floats<BN, CP>()>(p, acc, smem, tile * BM, 0, wave * 64, 0, tid, li, lh, 0, b, tyi * TH, txi * TW);
 }
 
-struct TileCfg {
-    int BM, BN, BK;
-};
+// ---- host side: knobs -> route (conv_route.h) -> launch -----------------------------------------------------------------------------
+namespace route = gif_conv;
 
-// fp32: BK = 32 floats (LDS-DMA kernel) or 8 (register-staged kernel of the Cin < 32 layers).
-// f16 : BK = 64 halfs, LDS-DMA kernel only (channel counts are multiples of 8 there: every 16-byte DMA chunk is 8 halfs).
-template <typename T>
-inline TileCfg pick_cfg(int cout, int cin) {
-    TileCfg c;
-    // f16 also has a 128x64 tile: the 64-channel layers of the 512^2 / 1024^2 blocks would waste half of a 128-wide N tile
-    c.BN = cout <= 32 ? 32 : ((sizeof(T) == 2 && cout <= 64) ? 64 : 128);
-    c.BK = sizeof(T) == 2 ? 64 : (cin < 32 ? 8 : 32);
-    c.BM = c.BN == 32 ? 256 : 128;
-    return c;
-}
+static_assert(kRowsThinA == route::ROWS_THIN_A, "conv_route.h sizes the LDS of conv3x3_rows_thin_h2");
 
-template <typename K>
-int launch_kernel(K kern, GatherParams& p, int BM, int BN, int BK, hipStream_t s, gif::LdsAttr& attr) {
-    p.tiles_m = gif::cdiv(p.M - p.m_begin, BM);
-    p.tiles_n = p.RP / BN;
-    size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
-    attr.ensure(reinterpret_cast<const void*>(kern), lds);
-    dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
-    p.part_row0 = t_part_rows;
-    t_part_rows += p.tiles_m;
-    t_last_bm = BM;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
-    return 0;
-}
-
-template <int BM, int BN, int BK, int WMv, int WNv>
-int launch_simple(GatherParams& p, hipStream_t s) {
-    static gif::LdsAttr attr;
-    return launch_kernel(conv_gather_mfma<BM, BN, BK, WMv, WNv>, p, BM, BN, BK, s, attr);
-}
-
-// LDS bytes of the per-sample scale table and its geometry (elements of T)
-template <typename T, int BM>
-inline size_t scale_table(GatherParams& p) {
-    const int HWp = p.Hp * p.Wp;
-    int nb = (BM - 1) / HWp + 2;  // samples a BM-row tile can touch
-    if (nb > p.B) nb = p.B;
-    p.stab_nb = nb;
-    p.stab_stride = p.CP + 16 / (int)sizeof(T);  // + one 16-byte chunk: consecutive samples start 4 banks apart
-    return (size_t)nb * p.stab_stride * sizeof(T);
-}
-
-// LDS bytes of the double-buffered operand tiles: 128-byte rows; X3: the weight tile is three 64-byte-row bf16 tiles
-template <int BM, int BN, int X3, int NST = 2>
-constexpr size_t stage_bytes() { return X3 ? (size_t)NST * BM * 128 + (size_t)NST * (X3 == 2 ? 2 : 3) * BN * 64 : (size_t)2 * (BM + BN) * 128; }
-
-// GIF_H2_RING=2: two-stage operand ring in the 8-wave f16x2 kernels too (A/B)
-inline bool h2_ring3() {
-    static const int on = gif::knob("GIF_H2_RING") ? atoi(gif::knob("GIF_H2_RING")) != 2 : 1;
-    return on != 0;
-}
-
-template <typename T, int BM, int BN, int WMv, int WNv, bool SCALE, int X3 = 0, int NST = 2>
-int launch_glds_impl(GatherParams& p, hipStream_t s) {
-    constexpr int BK = 128 / sizeof(T);  // 128-byte LDS rows
-    static gif::LdsAttr attr;
-    p.tiles_m = gif::cdiv(p.M - p.m_begin, BM);
-    p.tiles_n = p.RP / BN;
-    size_t lds = stage_bytes<BM, BN, X3, NST>();
-    p.stab_nb = 0;
-    p.stab_stride = 0;
-    if (SCALE) lds += scale_table<T, BM>(p);
-    if (lds > 160 * 1024) return -100;  // fp32 caller falls back to the register-staged kernel
-    auto kern = conv_gather_mfma_glds<T, BM, BN, WMv, WNv, SCALE, BK, X3, NST>;
-    attr.ensure(reinterpret_cast<const void*>(kern), lds);
-    // passed as a kernel argument: a GOT load inside the K loop costs a scalar memory round trip + s_waitcnt per stage
-    p.zero = gif::zero_page16();
-    if (!p.zero) return -101;
-    p.part_row0 = t_part_rows;
-    t_part_rows += p.tiles_m;
-    t_last_bm = BM;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(64 * WMv * WNv), lds, s, p);
-    return 0;
-}
-
-// all phases in one launch (64x64 tiles for the low-resolution layers, 256x128 / 8 waves for the big bf16x3 ones: one grid
-// instead of up to eight launches with a partly filled last round each); returns -100 if the configuration does not fit
-template <typename T, bool SCALE, int X3 = 0, int BM = 64, int BN = 64, int WMv = 2, int WNv = 2, int NST = 2>
-int launch_glds_multi(GatherParams* ph, int nph, hipStream_t s) {
-    constexpr int BK = 128 / sizeof(T);
-    static gif::LdsAttr attr;
-    const float* zero_page = gif::zero_page16();
-    if (!zero_page) return -101;
-    MultiParams mp{};
-    size_t lds_max = 0;
-    int total = 0, rows = 0;
-    for (int i = 0; i < nph; ++i) {
-        GatherParams& p = ph[i];
-        p.tiles_m = gif::cdiv(p.M - p.m_begin, BM);
-        p.tiles_n = p.RP / BN;
-        size_t lds = stage_bytes<BM, BN, X3, NST>();
-        p.stab_nb = 0;
-        p.stab_stride = 0;
-        if (SCALE) lds += scale_table<T, BM>(p);
-        if (lds > lds_max) lds_max = lds;
-        p.zero = zero_page;
-        total += p.tiles_m * p.tiles_n;
-        p.part_row0 = t_part_rows + rows;
-        rows += p.tiles_m;
-        mp.ph[i] = p;
-        mp.wg_end[i] = total;
-    }
-    mp.nph = nph;
-    if (lds_max > 160 * 1024) return -100;
-    t_part_rows += rows;
-    t_last_bm = BM;
-    auto kern = conv_gather_mfma_glds_multi<T, BM, BN, WMv, WNv, SCALE, BK, X3, NST>;
-    attr.ensure(reinterpret_cast<const void*>(kern), lds_max);
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(64 * WMv * WNv), lds_max, s, mp);
-    return 0;
-}
-
-// conv3x3_rows_thin_h2: eligibility and launch (f16x2 launches of stride-1 3x3 layers with <= 32 output channels whose 256-row tiles are
-// whole image rows or 256-pixel pieces of one; GIF_H2_ROWS_THIN=0: the gather kernel, A/B)
-inline bool rows_thin_ok(const GatherParams& p) {
-    static const int off = gif::knob("GIF_H2_ROWS_THIN") ? atoi(gif::knob("GIF_H2_ROWS_THIN")) == 0 : 0;
-    const bool unit = (p.ddy == 1 || p.ddy == -1) && (p.ddx == 1 || p.ddx == -1) && p.dy0 + p.ddy == 0 && p.dx0 + p.ddx == 0;
-    return !off && p.x3 == 2 && !p.dense && !p.in_scale && p.nky == 3 && p.nkx == 3 && unit && p.is == 1 && p.os == 1 && p.ooy == 0 &&
-           p.oox == 0 && p.RP == 32 && p.CP % 32 == 0 && p.m_begin == 0 && p.M % 256 == 0 && p.Hp == p.Hi && p.Wp == p.Wi &&
-           p.Ho == p.Hp && p.Wo == p.Wp && (p.Wp % 256 == 0 || (p.Wp >= 32 && 256 % p.Wp == 0)) &&
-           ((long)p.B * p.Hi * p.Wi + p.Wi) * p.Ci * 4 < (1L << 32);
-}
-inline int launch_rows_thin(GatherParams& p, hipStream_t s) {
-    static gif::LdsAttr attr;
-    const size_t lds = (size_t)2 * kRowsThinA * 32 * sizeof(float);
-    p.tiles_m = p.M / 256;
-    p.tiles_n = 1;
-    p.stab_nb = 0;
-    p.stab_stride = 0;
-    attr.ensure(reinterpret_cast<const void*>(conv3x3_rows_thin_h2), lds);
-    p.zero = gif::zero_page16();
-    if (!p.zero) return -101;
-    p.part_row0 = t_part_rows;
-    t_part_rows += p.tiles_m;
-    t_last_bm = 256;
-    hipLaunchKernelGGL(conv3x3_rows_thin_h2, dim3((unsigned)p.tiles_m), dim3(256), lds, s, p);
-    return 0;
-}
-
-template <typename T, int BM, int BN, int WMv, int WNv>
-int launch_glds(GatherParams& p, hipStream_t s) {
-    if constexpr (sizeof(T) == 4) {
-        if constexpr (WNv == 1 || (BM == 64 && BN == 64)) {  // the wave layouts the f16x2 kernels are built for
-            if constexpr (WMv * WNv == 8) {
-                if (p.x3 == 2 && h2_ring3()) {
-                    const int rc = p.in_scale ? launch_glds_impl<T, BM, BN, WMv, WNv, true, 2, 3>(p, s)
-                                              : launch_glds_impl<T, BM, BN, WMv, WNv, false, 2, 3>(p, s);
-                    if (rc != -100) return rc;  // (-100: the scale table did not fit beside three stages)
-                }
-            }
-            if (p.x3 == 2)
-                return p.in_scale ? launch_glds_impl<T, BM, BN, WMv, WNv, true, 2>(p, s)
-                                  : launch_glds_impl<T, BM, BN, WMv, WNv, false, 2>(p, s);
-        }
-        if (p.x3 == 2) return -102;
-        if (p.x3)
-            return p.in_scale ? launch_glds_impl<T, BM, BN, WMv, WNv, true, 1>(p, s)
-                              : launch_glds_impl<T, BM, BN, WMv, WNv, false, 1>(p, s);
-    }
-    return p.in_scale ? launch_glds_impl<T, BM, BN, WMv, WNv, true>(p, s)
-                      : launch_glds_impl<T, BM, BN, WMv, WNv, false>(p, s);
-}
-
-// 256x128 tile of the bf16x3 path: 8 waves as 8 (M) x 1 (N) — wave tile 32 x 128: ONE activation fragment to split per 24 MFMAs
-// (the 4 x 2 layout splits two; GIF_X3_WAVES=42 selects it for A/B)
-template <typename T>
-int launch_big_x3(GatherParams& p, hipStream_t s) {
-    static const int layout = gif::knob("GIF_X3_WAVES") ? atoi(gif::knob("GIF_X3_WAVES")) : 81;
-    return (layout == 42 && p.x3 == 1) ? launch_glds<T, 256, 128, 4, 2>(p, s) : launch_glds<T, 256, 128, 8, 1>(p, s);
-}
-
-// 128x128 tile: 2 x 2 waves of 64 x 64; bf16x3: 4 x 1 waves of 32 x 128 (one activation fragment to split per 24 MFMAs)
-template <typename T>
-int launch_128(GatherParams& p, hipStream_t s) {
-    if constexpr (sizeof(T) == 4) {
-        static const int layout = gif::knob("GIF_X3_WAVES") ? atoi(gif::knob("GIF_X3_WAVES")) : 81;
-        if (p.x3 == 2 || (p.x3 && layout != 42)) return launch_glds<T, 128, 128, 4, 1>(p, s);
-    }
-    return launch_glds<T, 128, 128, 2, 2>(p, s);
-}
-
-template <typename T>
-int launch_multi(GatherParams* ph, int nph, bool scale, hipStream_t s) {
-    if constexpr (sizeof(T) == 4) {
-        if (ph[0].x3 == 2) return scale ? launch_glds_multi<T, true, 2>(ph, nph, s) : launch_glds_multi<T, false, 2>(ph, nph, s);
-        if (ph[0].x3) return scale ? launch_glds_multi<T, true, 1>(ph, nph, s) : launch_glds_multi<T, false, 1>(ph, nph, s);
-    }
-    return scale ? launch_glds_multi<T, true>(ph, nph, s) : launch_glds_multi<T, false>(ph, nph, s);
-}
-
-// f16 halo kernel: launch configuration (tiles_n == 1: RP <= 64 is one N tile)
-template <int BN, int CP>
-int launch_halo_impl(GatherParams& p, hipStream_t s) {
-    static gif::LdsAttr attr;
-    p.t2_tx = gif::cdiv(p.Wp, 16);
-    p.t2_ty = gif::cdiv(p.Hp, 16);
-    p.tiles_m = p.B * p.t2_tx * p.t2_ty;
-    p.tiles_n = 1;
-    const size_t lds = (size_t)halo_lds_floats<BN, CP>() * sizeof(float) + (size_t)p.ntaps * BN * CP * 2;
-    auto kern = conv_halo_f16<BN, CP>;
-#ifdef GIF_HALO_PROBE  // ablation bits of tools/probes (results are wrong when set): never in the production library
-    p.halo_dbg = gif::knob("GIF_HALO_DBG") ? atoi(gif::knob("GIF_HALO_DBG")) : 0;
-#else
-    p.halo_dbg = 0;
-#endif
-    attr.ensure(reinterpret_cast<const void*>(kern), lds);
-    p.zero = gif::zero_page16();
-    if (!p.zero) return -101;
-    p.part_row0 = t_part_rows;
-    t_part_rows += p.tiles_m;
-    t_last_bm = 256;
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.tiles_m), dim3(256), lds, s, p);
-    return 0;
+// The GIF_* variables of conv_route.h, read once per process.
+const route::ConvKnobs& conv_knobs() {
+    static const route::ConvKnobs once = [] {
+        route::ConvKnobs k;
+        const auto num = [](const char* name, int unset) { const char* e = gif::knob(name); return e ? atoi(e) : unset; };
+        k.h2_ring3 = num("GIF_H2_RING", 3) != 2;
+        k.h2_rows_thin = num("GIF_H2_ROWS_THIN", 1) != 0;
+        k.x3_waves = num("GIF_X3_WAVES", k.x3_waves);
+        k.f16_tile256 = num("GIF_F16_TILE256", 1) != 0;
+        k.x3_big = num("GIF_X3_BIG", 1) != 0;
+        k.dense128 = num("GIF_DENSE_TILE", 128) != 256;
+        k.x3_multi_big = num("GIF_X3_MULTI_BIG", 1) != 0;
+        k.conv_variant = num("GIF_CONV_VARIANT", 0);
+        k.f16_halo = num("GIF_F16_HALO", 1) != 0;
+        k.halo_dbg = num("GIF_HALO_DBG", 0);
+        return k;
+    }();
+    return once;
 }
 
 // GIF_F16_HALO=0 / gif_conv2d_f16_halo_enable(0): the gather kernel everywhere (A/B knob; read once, tests use the setter)
 inline std::atomic<int>& halo_switch() {
-    static std::atomic<int> on{gif::knob("GIF_F16_HALO") ? (atoi(gif::knob("GIF_F16_HALO")) != 0) : 1};
+    static std::atomic<int> on{conv_knobs().f16_halo ? 1 : 0};
     return on;
 }
 
-// bytes of the weight slices a halo launch stages in LDS: [ntaps][BN][CP] halfs
-inline long halo_weight_bytes(const GatherParams& p) {
-    const int bn = p.RP <= 32 ? 32 : 64, cp = p.CP <= 32 ? 32 : 64;
-    return (long)p.ntaps * bn * cp * 2;
+// the geometry of one phase and what a launch adds to it (the rows, the tiling, the scale table, the partial-sum rows)
+void fill_phase(GatherParams& p, const route::ConvPhase& q) {
+    p.B = q.B; p.Hi = q.Hi; p.Wi = q.Wi; p.Ci = q.Ci;
+    p.Ho = q.Ho; p.Wo = q.Wo; p.Co = q.Co;
+    p.Hp = q.Hp; p.Wp = q.Wp; p.os = q.os; p.ooy = q.ooy; p.oox = q.oox; p.is = q.is;
+    p.ntaps = q.ntaps; p.nky = q.nky; p.nkx = q.nkx; p.dy0 = q.dy0; p.ddy = q.ddy; p.dx0 = q.dx0; p.ddx = q.ddx;
+    p.ky0 = q.ky0; p.kx0 = q.kx0; p.kstep = q.kstep; p.KW = q.KW;
+    p.RP = q.RP; p.CP = q.CP; p.M = q.M; p.m_begin = 0;
+    p.x3 = q.x3; p.dense = q.dense; p.pair = q.pair; p.no_split = q.no_split;
+}
+GatherParams launch_params(const GatherParams& phase, const route::ConvLaunch& l, int i, const void* zero) {
+    GatherParams p = phase;
+    if (l.kernel != route::CONV_GLDS_MULTI) { p.m_begin = l.m_begin; p.M = l.M; }
+    p.tiles_m = l.tiles_m[i]; p.tiles_n = l.tiles_n;
+    p.stab_nb = l.stab_nb[i]; p.stab_stride = l.stab_stride;
+    p.t2_tx = l.t2_tx; p.t2_ty = l.t2_ty;
+    p.part_row0 = l.part_row0[i];
+    // passed as a kernel argument: a GOT load inside the K loop costs a scalar memory round trip + s_waitcnt per stage
+    p.zero = zero;
+    return p;
 }
 
-// Which f16 launches take the halo kernel: unit-stride gathers (forward stride 1, every data gradient incl. the output-parity
-// phases of a transposed convolution) over a tap grid of <= 3 x 3 with <= 64 contraction and <= 64 output channels, on a
-// sub-grid that fills at least one patch.  The modulation-gradient dot fusion needs whole patches (one partial row per patch,
-// Hp * Wp / 256 of them per sample).  GIF_F16_HALO=0: A/B knob (the gather kernel).
-inline bool halo_eligible(const GatherParams& p) {
-    if (!halo_switch().load(std::memory_order_relaxed) || p.is != 1 || p.RP > 64 || p.CP > 64 || p.m_begin != 0) return false;
-    if (p.nky < 1 || p.nky > 3 || p.nkx < 1 || p.nkx > 3 || (p.ddy != 1 && p.ddy != -1) || (p.ddx != 1 && p.ddx != -1)) return false;
-    if (p.Hp < 16 || p.Wp < 16 || (long)p.B * gif::cdiv(p.Hp, 16) * gif::cdiv(p.Wp, 16) >= (1L << 23)) return false;
-    if (p.part_dot && (p.Hp % 16 || p.Wp % 16)) return false;
-    if (halo_weight_bytes(p) > 36864) return false;  // 9 taps of 64 x 64 channels (72 KB) stay on the gather kernel
+template <typename K, typename P>
+void launch_kernel(K kern, gif::LdsAttr& attr, const route::ConvLaunch& l, const P& p, hipStream_t s) {
+    attr.ensure(reinterpret_cast<const void*>(kern), l.lds_bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(l.threads), l.lds_bytes, s, p);
+}
+
+// Each *_try launches its instantiation iff `l` names exactly it.
+template <int BM, int BN, int BK, int WMv, int WNv>
+bool simple_try(const route::ConvLaunch& l, const GatherParams& p, hipStream_t s) {
+    if (l.BM != BM || l.BN != BN || l.BK != BK) return false;
+    static gif::LdsAttr attr;
+    launch_kernel(conv_gather_mfma<BM, BN, BK, WMv, WNv>, attr, l, p, s);
     return true;
 }
 
-int launch_halo(GatherParams& p, hipStream_t s) {
-    if (p.RP <= 32) return p.CP <= 32 ? launch_halo_impl<32, 32>(p, s) : launch_halo_impl<32, 64>(p, s);
-    return p.CP <= 32 ? launch_halo_impl<64, 32>(p, s) : launch_halo_impl<64, 64>(p, s);
+template <typename T, int BM, int BN, int WMv, int WNv, bool SCALE, int X3, int NST>
+void glds_run(const route::ConvLaunch& l, const GatherParams& p, hipStream_t s) {
+    static gif::LdsAttr attr;
+    launch_kernel(conv_gather_mfma_glds<T, BM, BN, WMv, WNv, SCALE, 128 / sizeof(T), X3, NST>, attr, l, p, s);  // 128-byte LDS rows
+}
+template <typename T, int BM, int BN, int WMv, int WNv, int X3, int NST = 2>
+bool glds_try(const route::ConvLaunch& l, const GatherParams& p, hipStream_t s) {
+    if (l.X3 != X3 || l.NST != NST) return false;
+    l.SCALE ? glds_run<T, BM, BN, WMv, WNv, true, X3, NST>(l, p, s) : glds_run<T, BM, BN, WMv, WNv, false, X3, NST>(l, p, s);
+    return true;
+}
+// The operand formats one tile is built for: its own MFMA always; fp32 tiles also bf16x3, and f16x2 in the wave layouts that leave N
+// undivided (or 64x64), with three stages on 8 waves.
+template <typename T, int BM, int BN, int WMv, int WNv>
+bool glds_tile(const route::ConvLaunch& l, const GatherParams& p, hipStream_t s) {
+    if (l.f16 != (sizeof(T) == 2) || l.BM != BM || l.BN != BN || l.WM != WMv || l.WN != WNv) return false;
+    if constexpr (sizeof(T) == 4) {
+        if constexpr (WNv == 1 || (BM == 64 && BN == 64)) {
+            if constexpr (WMv * WNv == 8)
+                if (glds_try<T, BM, BN, WMv, WNv, 2, 3>(l, p, s)) return true;
+            if (glds_try<T, BM, BN, WMv, WNv, 2>(l, p, s)) return true;
+        }
+        if (glds_try<T, BM, BN, WMv, WNv, 1>(l, p, s)) return true;
+    }
+    return glds_try<T, BM, BN, WMv, WNv, 0>(l, p, s);
 }
 
-// GIF_CONV_VARIANT=1 forces the register-staged kernel everywhere (A/B benchmarking only)
-int conv_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = gif::knob("GIF_CONV_VARIANT");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
+template <typename T, int BM, int BN, int WMv, int WNv, bool SCALE, int X3, int NST>
+void multi_run(const route::ConvLaunch& l, const MultiParams& mp, hipStream_t s) {
+    static gif::LdsAttr attr;
+    launch_kernel(conv_gather_mfma_glds_multi<T, BM, BN, WMv, WNv, SCALE, 128 / sizeof(T), X3, NST>, attr, l, mp, s);
+}
+template <typename T, int BM, int BN, int WMv, int WNv, int X3, int NST = 2>
+bool multi_try(const route::ConvLaunch& l, const MultiParams& mp, hipStream_t s) {
+    if (l.f16 != (sizeof(T) == 2) || l.BM != BM || l.BN != BN || l.WM != WMv || l.WN != WNv || l.X3 != X3 || l.NST != NST) return false;
+    l.SCALE ? multi_run<T, BM, BN, WMv, WNv, true, X3, NST>(l, mp, s) : multi_run<T, BM, BN, WMv, WNv, false, X3, NST>(l, mp, s);
+    return true;
 }
 
-template <typename T>
-int launch(GatherParams& p, hipStream_t s) {
-    constexpr bool F16 = sizeof(T) == 2;
-    if (p.M <= 0 || p.ntaps <= 0) return 0;
-    if ((long)p.B * p.Hi * p.Wi * p.Ci >= (1L << 31) || (long)p.B * p.Ho * p.Wo * p.Co >= (1L << 31)) {
-        gif::set_error("conv: tensors of >= 2^31 elements are not supported (32-bit offsets)");
-        return GIF_ENOSUP;
+template <int BN, int CP>
+bool halo_try(const route::ConvLaunch& l, const GatherParams& p, hipStream_t s) {
+    static_assert(halo_lds_floats<BN, CP>() == route::halo_lds_floats(CP), "conv_route.h sizes the LDS of conv_halo_f16");
+    if (l.BN != BN || l.HCP != CP) return false;
+    static gif::LdsAttr attr;
+    launch_kernel(conv_halo_f16<BN, CP>, attr, l, p, s);
+    return true;
+}
+
+// One launch of a route over the op's phases.  The ladders below are the complete list of the tiles the library carries.
+int conv_dispatch(const route::ConvLaunch& l, const GatherParams* ph, hipStream_t s, const char* who) {
+    using gif::f16;
+    const void* zero = nullptr;
+    if (l.kernel != route::CONV_SIMPLE) {
+        zero = gif::zero_page16();
+        GIF_REQUIRE(zero, "%s: zero page lookup failed", who);
     }
-    if ((p.x3 || F16) && ((long)p.B * p.Hi * p.Wi * p.Ci * (long)sizeof(T) > (1L << 32) - (1L << 26) || p.nky * p.nkx > 32)) {
+    bool launched = false;
+    if (l.kernel == route::CONV_GLDS_MULTI) {
+        MultiParams mp{};
+        int total = 0;
+        for (int i = 0; i < l.nph; ++i) {
+            mp.ph[i] = launch_params(ph[l.phase0 + i], l, i, zero);
+            total += l.tiles_m[i] * l.tiles_n;
+            mp.wg_end[i] = total;
+        }
+        mp.nph = l.nph;
+        launched = multi_try<float, 64, 64, 2, 2, 0>(l, mp, s) || multi_try<float, 64, 64, 2, 2, 1>(l, mp, s) ||
+                   multi_try<float, 64, 64, 2, 2, 2>(l, mp, s) || multi_try<float, 256, 128, 8, 1, 1>(l, mp, s) ||
+                   multi_try<float, 256, 128, 8, 1, 2>(l, mp, s) || multi_try<float, 256, 128, 8, 1, 2, 3>(l, mp, s) ||
+                   multi_try<f16, 64, 64, 2, 2, 0>(l, mp, s);
+    } else {
+        GatherParams p = launch_params(ph[l.phase0], l, 0, zero);
+        switch (l.kernel) {
+        case route::CONV_SIMPLE:
+            launched = simple_try<128, 128, 32, 2, 2>(l, p, s) || simple_try<128, 128, 8, 2, 2>(l, p, s) ||
+                       simple_try<256, 32, 32, 4, 1>(l, p, s) || simple_try<256, 32, 8, 4, 1>(l, p, s);
+            break;
+        case route::CONV_GLDS:
+            launched = glds_tile<float, 128, 128, 2, 2>(l, p, s) || glds_tile<float, 128, 128, 4, 1>(l, p, s) ||
+                       glds_tile<float, 256, 128, 8, 1>(l, p, s) || glds_tile<float, 256, 128, 4, 2>(l, p, s) ||
+                       glds_tile<float, 128, 64, 4, 1>(l, p, s) || glds_tile<float, 64, 64, 2, 2>(l, p, s) ||
+                       glds_tile<float, 256, 32, 4, 1>(l, p, s) ||
+                       glds_tile<f16, 256, 256, 2, 4>(l, p, s) || glds_tile<f16, 128, 128, 2, 2>(l, p, s) ||
+                       glds_tile<f16, 128, 64, 2, 2>(l, p, s) || glds_tile<f16, 64, 64, 2, 2>(l, p, s) ||
+                       glds_tile<f16, 256, 32, 4, 1>(l, p, s);
+            break;
+        case route::CONV_ROWS_THIN: {
+            static gif::LdsAttr attr;
+            launch_kernel(conv3x3_rows_thin_h2, attr, l, p, s);
+            launched = true;
+            break;
+        }
+        case route::CONV_HALO:
+#ifdef GIF_HALO_PROBE  // ablation bits of tools/probes (results are wrong when set): never in the production library
+            p.halo_dbg = conv_knobs().halo_dbg;
+#else
+            p.halo_dbg = 0;
+#endif
+            launched = halo_try<32, 32>(l, p, s) || halo_try<32, 64>(l, p, s) || halo_try<64, 32>(l, p, s) || halo_try<64, 64>(l, p, s);
+            break;
+        }
+    }
+    GIF_REQUIRE(launched, "%s: the route names a kernel that is not built (kind %d %s %dx%d waves %dx%d x3 %d stages %d)", who, l.kernel,
+                l.f16 ? "f16" : "f32", l.BM, l.BN, l.WM, l.WN, l.X3, l.NST);
+    return 0;
+}
+
+int route_error(const route::ConvRoute& r) {
+    const char* fmt = r.f16 ? "f16" : "bf16x3";
+    switch (r.error) {
+    case route::CONV_OK: return 0;
+    case route::CONV_ERR_2G: gif::set_error("conv: tensors of >= 2^31 elements are not supported (32-bit offsets)"); break;
+    case route::CONV_ERR_DMA:
         gif::set_error("conv (%s): the buffer-addressed activation DMA takes < 4 GiB of input and <= 32 taps (%ld elements, %d taps)%s",
-                       F16 ? "f16" : "bf16x3", (long)p.B * p.Hi * p.Wi * p.Ci, p.nky * p.nkx, F16 ? "" : ": use the _f32 entry point");
-        return GIF_ENOSUP;
-    }
-    TileCfg c = pick_cfg<T>(p.Co, p.Ci);
-    if (p.x3) c.BK = 32;
-    // LDS-DMA path: every layer whose K chunk is a 128-byte row (rows are 16-byte aligned in HBM: Ci % 4 == 0 for fp32,
-    // Ci % 8 == 0 for f16)
-    const bool only_glds = F16 || p.x3;  // no register-staged fallback for these operand formats
-    const bool glds = only_glds || (c.BK == 32 && conv_variant() != 1);
-    auto fail_f16 = [&](int rc) {
-        if (rc != 0) gif::set_error("conv (%s): launch configuration does not fit (rc=%d)", F16 ? "f16" : "bf16x3", rc);
-        return rc == 0 ? 0 : GIF_ENOSUP;
-    };
-    if (p.x3 && p.Ci < 24 && !p.dense) {
-        gif::set_error("conv (bf16x3): needs >= 24 input channels (gif_conv2d_x3_eligible)");
-        return GIF_ENOSUP;
-    }
-    if constexpr (F16) {
-        if (halo_eligible(p) && launch_halo(p, s) == 0) return 0;
-        if (c.BN == 64) return fail_f16(launch_glds<T, 128, 64, 2, 2>(p, s));
-        // f16 MFMAs are 8x shorter than fp32 ones while an LDS-DMA piece costs the same to issue: on 128x128 tiles a wave issues
-        // one 1-KiB piece per two MFMAs and the loop is bound by DMA issue + LDS traffic, not by the matrix pipe.  Layers with
-        // >= 256 output channels and enough rows run 256x256 tiles on 8 waves (2 x 4, wave tile 128x64: one piece per four
-        // MFMAs, 0.75 instead of 1 operand read per MFMA; 128 KB of LDS, one workgroup per CU): 512->512 at 64^2 780 -> 886
-        // TFLOP/s, 256->256 at 128^2 710 -> 752.  GIF_F16_TILE256=0: A/B knob.
-        static const int t256_off = gif::knob("GIF_F16_TILE256") ? atoi(gif::knob("GIF_F16_TILE256")) == 0 : 0;
-        if (!t256_off && c.BN == 128 && p.RP % 256 == 0 && (long)gif::cdiv(p.M, 256) * (p.RP / 256) >= 512 &&
-            launch_glds<T, 256, 256, 2, 4>(p, s) == 0)
-            return 0;
-    }
-    if (c.BN == 128 && (F16 || c.BK == 32)) {
-        // low-resolution layers (4x4 .. 16x16 at batch 32): a 128x128 grid would leave most CUs idle behind a
-        // 144-step K loop; 64x64 tiles give 4x the workgroups (and 32 KB of LDS: 4 per CU) at a quarter of the latency
-        const long tiles128 = (long)gif::cdiv(p.M, 128) * (p.RP / 128);
-        if constexpr (!F16) {
-            // low-resolution bf16x3 layers with at least one workgroup per CU: 128x64 tiles, 4 waves stacked along M (wave tile
-            // 32x64: one activation fragment split per 12 MFMAs instead of per 6 on the 64x64 tile's 32x32 wave tiles) — 512->512 at
-            // 16^2 143 -> 165 TFLOP/s, modulated 127 -> 157, stride-2 512->512 at 33^2 142 -> 170 (profiles/r3_dispatch_ab.txt)
-            if (p.x3 && tiles128 < 384 && (long)gif::cdiv(p.M, 128) * (p.RP / 64) >= 256 &&
-                launch_glds<T, 128, 64, 4, 1>(p, s) == 0)
-                return 0;
-        }
-        if (glds && tiles128 < 384 && launch_glds<T, 64, 64, 2, 2>(p, s) == 0) return 0;
-        if constexpr (!F16) {
-            // bf16x3: the pre-split weight tile (48 KB) + the fp32 activation tile (32 KB) fill half a CU's LDS exactly, and a
-            // modulated conv's scale table no longer fits beside them.  Big layers run 256x128 tiles on 8 waves instead: one
-            // workgroup per CU (112 KB + table), still two waves per SIMD, a quarter less operand traffic per MFMA.
-            static const int big_off = gif::knob("GIF_X3_BIG") ? atoi(gif::knob("GIF_X3_BIG")) == 0 : 0;
-            const long tn = p.RP / 128, tiles256 = (long)gif::cdiv(p.M, 256) * tn;
-            // tap-dense layers (K = 9 taps x 8..28 channels: 3..7 stages): one 8-wave workgroup per CU spends most of a tile in its
-            // prologue and epilogue with nothing else resident; two 4-wave workgroups per CU on 128x128 tiles: 24 -> 256 at 128^2 129 ->
-            // 133 TFLOP/s, 24 -> 512 at 64^2 130 -> 134, the family in the step 8.57 -> 8.19 ms (GIF_DENSE_TILE=256: A/B)
-            static const int dense128 = gif::knob("GIF_DENSE_TILE") ? atoi(gif::knob("GIF_DENSE_TILE")) != 256 : 1;
-            if (p.x3 && !big_off && tiles256 >= 512 && !(p.dense && dense128)) {
-                const long slots = 256, full = tiles256 / slots, rem = tiles256 % slots;
-                if (!p.no_split && rem > 0 && rem * 2 <= slots && slots % tn == 0) {  // nearly empty last round: remainder rows on 64x64 tiles
-                    const int M = p.M;
-                    const int m_bulk = (int)(full * slots / tn) * 256;
-                    p.M = m_bulk;
-                    if (launch_big_x3<T>(p, s) == 0) {
-                        p.M = M;
-                        p.m_begin = m_bulk;
-                        int rc = launch_glds<T, 64, 64, 2, 2>(p, s);
-                        p.m_begin = 0;
-                        return rc;
-                    }
-                    p.M = M;
-                } else if (launch_big_x3<T>(p, s) == 0) {
-                    return 0;
-                }
-            }
-        }
-        if (glds && conv_variant() != 3) {
-            // Tile quantisation: 512 workgroups of this kernel are resident (2 per CU), so T tiles cost ceil(T / 512) rounds.
-            // The odd-sized phase grids of the transposed convolutions (129^2, 65^2, 33^2 pixels) give e.g. 4161 or 1092
-            // tiles = 8.13 / 2.13 rounds: the nearly empty last round costs 10-30 %.  Split such launches: the full rounds
-            // on 128x128 tiles, the remaining rows on 64x64 tiles (4x the workgroups, a quarter of the latency each).
-            const long slots = 512, tn = p.RP / 128;
-            const long full = tiles128 / slots, rem = tiles128 % slots;
-            if (!p.no_split && full >= 1 && rem > 0 && rem * 2 <= slots && slots % tn == 0) {
-                const int M = p.M;
-                const int m_bulk = (int)(full * slots / tn) * 128;
-                p.M = m_bulk;
-                if (launch_128<T>(p, s) == 0) {
-                    p.M = M;
-                    p.m_begin = m_bulk;
-                    int rc = launch_glds<T, 64, 64, 2, 2>(p, s);
-                    p.m_begin = 0;
-                    return rc;
-                }
-                p.M = M;
-            }
-        }
-        if (glds) {
-            int rc = launch_128<T>(p, s);
-            if (rc == 0) return 0;
-            if (only_glds) return fail_f16(rc);
-        }
-        if constexpr (!F16) return launch_simple<128, 128, 32, 2, 2>(p, s);
-    }
-    if constexpr (!F16) {
-        if (rows_thin_ok(p)) return launch_rows_thin(p, s);  // f16x2, stride-1 3x3, <= 32 output channels: rows + halo staged once per kernel row
-    }
-    if (only_glds) return fail_f16(launch_glds<T, 256, 32, 4, 1>(p, s));
-    if constexpr (!F16) {
-        if (c.BN == 128 && c.BK == 8) return launch_simple<128, 128, 8, 2, 2>(p, s);
-        if (c.BN == 32 && c.BK == 32) {
-            if (glds && launch_glds<T, 256, 32, 4, 1>(p, s) == 0) return 0;
-            return launch_simple<256, 32, 32, 4, 1>(p, s);
-        }
-        return launch_simple<256, 32, 8, 4, 1>(p, s);
+                       fmt, r.err_elems, r.err_taps, r.f16 ? "" : ": use the _f32 entry point");
+        break;
+    case route::CONV_ERR_X3_CIN: gif::set_error("conv (bf16x3): needs >= 24 input channels (gif_conv2d_x3_eligible)"); break;
+    default: gif::set_error("conv (%s): launch configuration does not fit (rc=%d)", fmt, r.err_rc);
     }
     return GIF_ENOSUP;
 }
@@ -2180,8 +1981,7 @@ struct FusedSums {
 
     bool active() const { return colsum || dot; }
 
-    int begin(GatherParams& p, const gif_conv_epilogue* e, long out_rows, int Co, int B, long hw, bool single_phase, const char* who) {
-        t_part_rows = 0;
+    int begin(GatherParams& p, const gif_conv_epilogue* e, long out_rows, int Co, long hw, bool single_phase, const char* who) {
         if (!e || (!e->colsum && !e->dot)) return 0;
         GIF_REQUIRE(e->red_ws, "%s: colsum / dot need the red_ws workspace (gif_conv_epilogue_ws_floats)", who);
         GIF_REQUIRE(!e->dot || (e->dot_src && single_phase && hw % 256 == 0),
@@ -2195,39 +1995,27 @@ struct FusedSums {
         p.part_cs = colsum ? part_cs : nullptr;
         p.part_dot = dot ? part_dot : nullptr;
         p.part_cap = (int)cap;
-        p.no_split = dot ? 1 : 0;
-        (void)B;
         return 0;
     }
-    int finish(int Co, int B, long hw, hipStream_t s, const char* who) {
+    // rows / tile_rows: how the route cut the op into tiles (ConvRoute::part_rows, tile_rows)
+    int finish(int Co, int B, long hw, int rows, int tile_rows, hipStream_t s, const char* who) {
         if (!colsum && !dot) return 0;
-        const int rows = t_part_rows;
         GIF_REQUIRE(rows > 0 && rows <= cap, "%s: partial-sum rows %d exceed the workspace (%ld)", who, rows, cap);
         if (colsum)
             if (int rc = gif::reduce_partials(part_cs, colsum, 1, rows, Co, tmp, s)) return rc;
         if (dot) {
-            GIF_REQUIRE(t_last_bm > 0 && hw % t_last_bm == 0 && (long)rows * t_last_bm == (long)B * hw,
-                        "%s: dot fusion: tiles of %d rows do not partition the %d samples of %ld pixels", who, t_last_bm, B, hw);
-            if (int rc = gif::reduce_partials(part_dot, dot, B, (int)(hw / t_last_bm), Co, tmp, s)) return rc;
+            GIF_REQUIRE(tile_rows > 0 && hw % tile_rows == 0 && (long)rows * tile_rows == (long)B * hw,
+                        "%s: dot fusion: tiles of %d rows do not partition the %d samples of %ld pixels", who, tile_rows, B, hw);
+            if (int rc = gif::reduce_partials(part_dot, dot, B, (int)(hw / tile_rows), Co, tmp, s)) return rc;
         }
         return 0;
     }
 };
 
-
-template <typename T>
-void pack_dims(int cout, int cin, int* RP, int* CP, bool x3 = false) {
-    TileCfg c = pick_cfg<T>(cout, cin);
-    if (x3) c.BK = 32;  // the bf16x3 kernels only have 32-float K chunks: 24..31 input channels are zero-padded to one chunk
-    *RP = (cout + c.BN - 1) / c.BN * c.BN;
-    *CP = (cin + c.BK - 1) / c.BK * c.BK;
-    if (sizeof(T) == 2 && cin <= 32) *CP = 32;  // "pair" mode of the f16 kernel: two taps per 64-half K chunk (GatherParams::pair)
-}
-
 // f16x2 launches: the packing is [header: RP row exponents + flag][planes]; the launch gets a fresh gate word (common.h)
-inline int h2_operands(GatherParams& p, const void* wp2, const void* wp_fallback, hipStream_t s) {
+inline int h2_operands(GatherParams& p, int RP, const void* wp2, const void* wp_fallback, hipStream_t s) {
     p.wexp = static_cast<const int*>(wp2);
-    p.wp = static_cast<const char*>(wp2) + gif::h2_header_bytes(p.RP);
+    p.wp = static_cast<const char*>(wp2) + gif::h2_header_bytes(RP);
     p.gate = nullptr; p.gate_gen = 0; p.h2_stats = nullptr;
     if (wp_fallback) {
         const gif::H2Gate gt = gif::h2_next_gate(s);
@@ -2252,51 +2040,84 @@ int check_channels(const gif_conv_geom* g, const char* who) {
 }
 
 template <typename T>
+route::ConvShape conv_shape(const gif_conv_geom* g, const gif_conv_epilogue* e, int x3, bool dense) {
+    return route::ConvShape{g->B, g->Hb, g->Wb, g->Cb, g->Hs, g->Ws, g->Cs, g->KH, g->KW, g->stride, g->pad,
+                            sizeof(T) == 2, x3, dense, e && e->in_scale, e && e->dot};
+}
+
+// The op's pointers, epilogue and f16x2 gate: the parameters every phase shares.
+template <typename T>
+int base_params(GatherParams& p, const void* x, const void* wp, void* y, const gif_conv_epilogue* e, int x3, int RP, const void* wp_fallback,
+                hipStream_t s) {
+    p.x = x; p.wp = wp; p.y = y; p.x3 = x3;
+    fill_epilogue(p, e);
+    if (sizeof(T) == 2) p.sat_flag = gif::f16_sat_flag();
+    return x3 == 2 ? h2_operands(p, RP, wp, wp_fallback, s) : 0;
+}
+
+// Route and launches of one op over its phases, the guarded bf16x3 twin of an f16x2 op included (a no-op unless the gate was raised), and
+// the reduction of its fused sums.  dims: what the profiling record shows.
+template <typename T>
+int conv_run(const GatherParams& base, const route::ConvPhases& phs, const void* wp_fallback, FusedSums& sums, double flops, int d0, int d3,
+             int B, long hw, hipStream_t s, const char* who, const char* twin_note) {
+    const bool halo_on = halo_switch().load(std::memory_order_relaxed) != 0;
+    const route::ConvRoute r = route::conv_route(phs.ph, phs.nph, sizeof(T) == 2, conv_knobs(), halo_on);
+    const bool guarded = base.x3 == 2 && base.gate && wp_fallback;
+    route::ConvPhases twin = phs;
+    route::ConvRoute r2{};
+    if (guarded) {
+        for (route::ConvPhase& q : twin.ph) q.x3 = 1;
+        r2 = route::conv_route(twin.ph, twin.nph, false, conv_knobs(), halo_on);
+        // FusedSums::finish reduces the per-tile partials through (part_rows, tile_rows): normally those rows were written by the
+        // f16x2 launch, so the twin must cut the op into the SAME tiles
+        if (!r.error && !r2.error && sums.active() && (r2.part_rows != r.part_rows || r2.tile_rows != r.tile_rows)) {
+            gif::set_error("%s: the guarded bf16x3 twin tiles the op differently from the f16x2 launch (%d x %d vs %d x %d rows)%s", who,
+                           r2.part_rows, r2.tile_rows, r.part_rows, r.tile_rows, twin_note);
+            return GIF_ENOSUP;
+        }
+    }
+    const route::ConvPhase& q0 = phs.ph[0];
+    gif::ProfScope prof(r.family, flops, s, d0, q0.Co, q0.Ci, d3);
+    GatherParams ph[4];
+    for (int i = 0; i < phs.nph; ++i) {
+        ph[i] = base;
+        fill_phase(ph[i], phs.ph[i]);
+    }
+    if (r.error) return route_error(r);
+    for (int i = 0; i < r.nlaunch; ++i)
+        if (int rc = conv_dispatch(r.launch[i], ph, s, who)) return rc;
+    if (guarded) {
+        for (int i = 0; i < phs.nph; ++i) {
+            h2_to_fallback(ph[i], wp_fallback);
+            if (i) ph[i].h2_stats = nullptr;  // gif_h2_fallback_stats counts OPS: only the first phase's twin reports
+        }
+        if (r2.error) return route_error(r2);
+        for (int i = 0; i < r2.nlaunch; ++i)
+            if (int rc = conv_dispatch(r2.launch[i], ph, s, who)) return rc;
+    }
+    return sums.finish(q0.Co, B, hw, r.part_rows, r.tile_rows, s, who);
+}
+
+template <typename T>
 int conv2d_fwd_impl(const void* big, const void* wp, void* small, const gif_conv_geom* g, const gif_conv_epilogue* e,
                     gif_stream_t stream, const char* who, int x3 = 0, bool dense = false, const void* wp_fallback = nullptr) {
     if (int rc = check_geom(g, who)) return rc;
     if (int rc = check_channels<T>(g, who)) return rc;
     if (g->B == 0) return 0;
     GIF_REQUIRE(big && wp && small, "%s: null pointer", who);
-    GatherParams p{};
-    p.x = big; p.wp = wp; p.y = small; p.x3 = x3;
-    fill_epilogue(p, e);
-    if (sizeof(T) == 2) p.sat_flag = gif::f16_sat_flag();
-    p.B = g->B; p.Hi = g->Hb; p.Wi = g->Wb; p.Ci = g->Cb;
-    p.Ho = g->Hs; p.Wo = g->Ws; p.Co = g->Cs;
-    p.Hp = g->Hs; p.Wp = g->Ws; p.os = 1; p.ooy = 0; p.oox = 0; p.is = g->stride;
-    p.nky = g->KH; p.nkx = g->KW; p.ntaps = g->KH * g->KW;
-    p.dy0 = -g->pad; p.ddy = 1; p.dx0 = -g->pad; p.ddx = 1;
-    p.ky0 = 0; p.kx0 = 0; p.kstep = 1; p.KW = g->KW;
-    pack_dims<T>(p.Co, p.Ci, &p.RP, &p.CP, x3 != 0);
-    p.pair = (sizeof(T) == 2 && p.CP == 32) ? 1 : 0;
-    if (dense) {
+    hipStream_t s = gif::as_stream(stream);
+    if (dense)
         if (int rc = check_tapdense(g, e, g->Cb, false, who)) return rc;
-        p.dense = g->Cb / 4;
-    }
-    if (x3 == 2)
-        if (int rc = h2_operands(p, wp, wp_fallback, gif::as_stream(stream))) return rc;
-    p.M = p.B * p.Hp * p.Wp;
-    double flops = 2.0 * p.M * (double)p.Co * p.Ci * p.ntaps;
-    const int fam = sizeof(T) == 2 ? 6 : dense ? (x3 == 2 ? 17 : 12) : x3 == 2 ? 13 : x3 ? 8 : (p.Ci >= 32 ? 0 : 5);
+    const route::ConvPhases phs = route::conv_phases_fwd(conv_shape<T>(g, e, x3, dense));
+    const route::ConvPhase& q = phs.ph[0];
+    GatherParams base{};
+    if (int rc = base_params<T>(base, big, wp, small, e, x3, q.RP, wp_fallback, s)) return rc;
     FusedSums sums;
-    if (int rc = sums.begin(p, e, p.M, p.Co, p.B, (long)p.Hp * p.Wp, true, who)) return rc;
-    gif::ProfScope prof(fam, flops, gif::as_stream(stream), p.M, p.Co, p.Ci, p.ntaps * 10 + g->stride);
-    if (int rc = launch<T>(p, gif::as_stream(stream))) return rc;
-    if (x3 == 2 && p.gate && wp_fallback) {  // guarded fallback: the same op on the bf16x3 kernels, a no-op unless the gate was raised
-        // FusedSums::finish reduces the per-tile partials through (t_part_rows, t_last_bm): normally those rows were written by the
-        // f16x2 launch, so the twin must cut the op into the SAME tiles (advisor, round 5: nothing else enforces it)
-        const int rows2 = t_part_rows, bm2 = t_last_bm;
-        h2_to_fallback(p, wp_fallback);
-        t_part_rows = 0;
-        if (int rc = launch<T>(p, gif::as_stream(stream))) return rc;
-        if (sums.active() && (t_part_rows != rows2 || t_last_bm != bm2)) {
-            gif::set_error("%s: the guarded bf16x3 twin tiles the op differently from the f16x2 launch (%d x %d vs %d x %d rows): fused "
-                           "column sums would mix partials", who, t_part_rows, t_last_bm, rows2, bm2);
-            return GIF_ENOSUP;
-        }
-    }
-    if (int rc = sums.finish(p.Co, p.B, (long)p.Hp * p.Wp, gif::as_stream(stream), who)) return rc;
+    if (int rc = sums.begin(base, e, q.M, q.Co, (long)q.Hp * q.Wp, true, who)) return rc;
+    const double flops = 2.0 * q.M * (double)q.Co * q.Ci * q.ntaps;
+    if (int rc = conv_run<T>(base, phs, wp_fallback, sums, flops, q.M, q.ntaps * 10 + g->stride, q.B, (long)q.Hp * q.Wp, s, who,
+                             ": fused column sums would mix partials"))
+        return rc;
     return gif::check_launch(who);
 }
 
@@ -2308,108 +2129,24 @@ int conv2d_bwd_data_impl(const void* small, const void* wp, void* big, const gif
     if (g->B == 0) return 0;
     GIF_REQUIRE(small && wp && big, "%s: null pointer", who);
     hipStream_t s = gif::as_stream(stream);
+    const route::ConvPhases phs = route::conv_phases_bwd_data(conv_shape<T>(g, e, x3, dense));
+    const route::ConvPhase& q = phs.ph[0];
     GatherParams base{};
-    base.x = small; base.wp = wp; base.y = big; base.x3 = x3;
-    fill_epilogue(base, e);
-    if (sizeof(T) == 2) base.sat_flag = gif::f16_sat_flag();
-    base.B = g->B; base.Hi = g->Hs; base.Wi = g->Ws; base.Ci = g->Cs;
-    base.Ho = g->Hb; base.Wo = g->Wb; base.Co = g->Cb;
-    pack_dims<T>(base.Co, base.Ci, &base.RP, &base.CP, x3 != 0);
-    base.pair = (sizeof(T) == 2 && base.CP == 32) ? 1 : 0;
-    if (x3 == 2)
-        if (int rc = h2_operands(base, wp, wp_fallback, s)) return rc;
-    if (dense) {
+    if (int rc = base_params<T>(base, small, wp, big, e, x3, q.RP, wp_fallback, s)) return rc;
+    if (dense)
         if (int rc = check_tapdense(g, e, g->Cs, true, who)) return rc;
-        base.dense = g->Cs / 4;
-    }
-    const int st = g->stride;
     FusedSums sums;
-    if (int rc = sums.begin(base, e, (long)g->B * g->Hb * g->Wb, base.Co, g->B, (long)g->Hb * g->Wb, st == 1, who)) return rc;
-    auto pmod = [st](int a) { return ((a % st) + st) % st; };
-    // Build the (up to 4) output-parity phases; phases with no tap (e.g. 1x1 stride 2) are zero-filled.
-    GatherParams ph[4];
-    int nph = 0;
-    bool need_zero = false;
-    for (int py = 0; py < st; ++py)
-        for (int px = 0; px < st; ++px) {
-            GatherParams p = base;
-            p.Hp = (g->Hb - py + st - 1) / st;
-            p.Wp = (g->Wb - px + st - 1) / st;
-            if (p.Hp <= 0 || p.Wp <= 0) continue;
-            p.os = st; p.ooy = py; p.oox = px; p.is = 1;
-            // taps with ky == (py+pad) mod st (and likewise kx): small pixel = big' + (py+pad-ky)/st
-            p.ky0 = pmod(py + g->pad); p.kx0 = pmod(px + g->pad); p.kstep = st; p.KW = g->KW;
-            p.nky = p.ky0 < g->KH ? (g->KH - p.ky0 + st - 1) / st : 0;
-            p.nkx = p.kx0 < g->KW ? (g->KW - p.kx0 + st - 1) / st : 0;
-            p.ntaps = p.nky * p.nkx;
-            p.dy0 = (py + g->pad - p.ky0) / st; p.ddy = -1;
-            p.dx0 = (px + g->pad - p.kx0) / st; p.ddx = -1;
-            if (p.ntaps == 0) { need_zero = true; continue; }
-            p.M = p.B * p.Hp * p.Wp;
-            ph[nph++] = p;
-        }
-    if (need_zero) {
+    if (int rc = sums.begin(base, e, (long)g->B * g->Hb * g->Wb, q.Co, (long)g->Hb * g->Wb, g->stride == 1, who)) return rc;
+    if (phs.need_zero) {  // phases with no tap (e.g. 1x1 stride 2) are zero-filled
         GIF_REQUIRE(!(e && (e->bias || e->residual || e->act || e->mask_src || e->colsum || e->dot)), "%s: epilogue unsupported with empty phases", who);
         hipError_t me = hipMemsetAsync(big, 0, (size_t)g->B * g->Hb * g->Wb * g->Cb * sizeof(T), s);
         if (me != hipSuccess) { gif::set_error("%s memset: %s", who, hipGetErrorString(me)); return (int)me; }
     }
     // algorithmic FLOPs of a transposed conv: every small-side pixel scatters through every tap
-    double flops = 2.0 * g->B * (double)g->Hs * g->Ws * g->KH * g->KW * (double)g->Cs * g->Cb;
-    {
-        const int fam = sizeof(T) == 2 ? 6 : dense ? (x3 == 2 ? 17 : 12) : x3 == 2 ? 13 : x3 ? 8 : (base.Ci >= 32 ? 0 : 5);
-        gif::ProfScope prof(fam, flops, s, g->B * g->Hb * g->Wb, base.Co, base.Ci, -(g->KH * g->KW * 10 + g->stride));
-        // small transposed convs: every phase alone would sit on the 64x64-tile path with a partly filled chip
-        auto run_phases = [&]() -> int {
-            bool merged = false;
-            if (nph > 1 && conv_variant() == 0) {
-                TileCfg c = pick_cfg<T>(base.Co, base.Ci);
-                if (x3) c.BK = 32;
-                bool small_all = c.BN == 128 && (sizeof(T) == 2 || c.BK == 32);
-                for (int i = 0; i < nph && small_all; ++i)
-                    small_all = (long)gif::cdiv(ph[i].M, 128) * (ph[i].RP / 128) < 384 &&
-                                (long)ph[i].B * ph[i].Hi * ph[i].Wi * ph[i].Ci < (1L << 31) &&
-                                (long)ph[i].B * ph[i].Ho * ph[i].Wo * ph[i].Co < (1L << 31);
-                if (small_all)
-                    merged = launch_multi<T>(ph, nph, base.in_scale != nullptr, s) == 0;
-                if constexpr (sizeof(T) == 4) {
-                    // big bf16x3 / f16x2 transposed convs: every phase would run 256x128 tiles on its own (bulk + remainder launch each)
-                    static const int big_multi_off = gif::knob("GIF_X3_MULTI_BIG") ? atoi(gif::knob("GIF_X3_MULTI_BIG")) == 0 : 0;
-                    bool big_all = x3 && !small_all && !big_multi_off && c.BN == 128;
-                    for (int i = 0; i < nph && big_all; ++i)
-                        big_all = (long)gif::cdiv(ph[i].M, 256) * (ph[i].RP / 128) >= 512 &&
-                                  (long)ph[i].B * ph[i].Hi * ph[i].Wi * ph[i].Ci < (1L << 31) &&
-                                  (long)ph[i].B * ph[i].Ho * ph[i].Wo * ph[i].Co < (1L << 31);
-                    if (big_all)
-                        merged = (ph[0].x3 == 2 ? (h2_ring3() ? (base.in_scale ? launch_glds_multi<T, true, 2, 256, 128, 8, 1, 3>(ph, nph, s)
-                                                                               : launch_glds_multi<T, false, 2, 256, 128, 8, 1, 3>(ph, nph, s))
-                                                              : (base.in_scale ? launch_glds_multi<T, true, 2, 256, 128, 8, 1>(ph, nph, s)
-                                                                               : launch_glds_multi<T, false, 2, 256, 128, 8, 1>(ph, nph, s)))
-                                                : (base.in_scale ? launch_glds_multi<T, true, 1, 256, 128, 8, 1>(ph, nph, s)
-                                                                 : launch_glds_multi<T, false, 1, 256, 128, 8, 1>(ph, nph, s))) == 0;
-                }
-            }
-            if (!merged)
-                for (int i = 0; i < nph; ++i)
-                    if (int rc = launch<T>(ph[i], s)) return rc;
-            return 0;
-        };
-        if (int rc = run_phases()) return rc;
-        if (x3 == 2 && base.gate && wp_fallback) {  // guarded fallback on the bf16x3 kernels (a no-op unless the gate was raised)
-            const int rows2 = t_part_rows, bm2 = t_last_bm;
-            for (int i = 0; i < nph; ++i) {
-                h2_to_fallback(ph[i], wp_fallback);
-                if (i) ph[i].h2_stats = nullptr;  // gif_h2_fallback_stats counts OPS: only the first phase's twin reports
-            }
-            t_part_rows = 0;
-            if (int rc = run_phases()) return rc;
-            if (sums.active() && (t_part_rows != rows2 || t_last_bm != bm2)) {  // (see conv2d_fwd_impl)
-                gif::set_error("%s: the guarded bf16x3 twin tiles the op differently from the f16x2 launch (%d x %d vs %d x %d rows)", who,
-                               t_part_rows, t_last_bm, rows2, bm2);
-                return GIF_ENOSUP;
-            }
-        }
-        if (int rc = sums.finish(base.Co, g->B, (long)g->Hb * g->Wb, s, who)) return rc;
-    }
+    const double flops = 2.0 * g->B * (double)g->Hs * g->Ws * g->KH * g->KW * (double)g->Cs * g->Cb;
+    if (int rc = conv_run<T>(base, phs, wp_fallback, sums, flops, g->B * g->Hb * g->Wb, -(g->KH * g->KW * 10 + g->stride), g->B,
+                             (long)g->Hb * g->Wb, s, who, ""))
+        return rc;
     return gif::check_launch(who);
 }
 
@@ -2419,13 +2156,13 @@ extern "C" {
 
 int gif_conv2d_pack_dims(int cout, int cin, int* RP, int* CP) {
     GIF_REQUIRE(cout > 0 && cin > 0 && RP && CP, "pack_dims: bad arguments");
-    pack_dims<float>(cout, cin, RP, CP);
+    route::pack_dims(false, cout, cin, false, RP, CP);
     return 0;
 }
 
 int gif_conv2d_pack_dims_f16(int cout, int cin, int* RP, int* CP) {
     GIF_REQUIRE(cout > 0 && cin > 0 && RP && CP, "pack_dims_f16: bad arguments");
-    pack_dims<gif::f16>(cout, cin, RP, CP);
+    route::pack_dims(true, cout, cin, false, RP, CP);
     return 0;
 }
 
@@ -2439,12 +2176,11 @@ int gif_conv2d_bwd_data_f32(const float* small, const float* wp, float* big, con
     return conv2d_bwd_data_impl<float>(small, wp, big, g, e, stream, "conv2d_bwd_data");
 }
 
-// >= 24 input channels: a 24-channel layer wastes a quarter of its one 32-float K chunk and still beats the native kernel
-int gif_conv2d_x3_eligible(int cout, int cin) { return cout > 0 && cin >= 24 && cin % 4 == 0 ? 1 : 0; }
+int gif_conv2d_x3_eligible(int cout, int cin) { return route::x3_eligible(cout, cin) ? 1 : 0; }
 
 int gif_conv2d_pack_dims_x3(int cout, int cin, int* RP, int* CP) {
     GIF_REQUIRE(cout > 0 && cin > 0 && RP && CP, "pack_dims_x3: bad arguments");
-    pack_dims<float>(cout, cin, RP, CP, true);
+    route::pack_dims(false, cout, cin, true, RP, CP);
     return 0;
 }
 
@@ -2494,13 +2230,8 @@ int gif_conv2d_f16_halo_enable(int on) {
     return 0;
 }
 
-// would a FORWARD f16 convolution of this shape (activation channel counts, output grid Hs x Ws) run the halo kernel?
 int gif_conv2d_f16_halo_eligible(int cin, int cout, int KH, int KW, int stride, int Hs, int Ws) {
-    if (cin <= 0 || cout <= 0 || KH < 1 || KW < 1 || stride < 1 || Hs <= 0 || Ws <= 0) return 0;
-    GatherParams p{};
-    pack_dims<gif::f16>(cout, cin, &p.RP, &p.CP);
-    p.is = stride; p.nky = KH; p.nkx = KW; p.ntaps = KH * KW; p.ddy = 1; p.ddx = 1; p.Hp = Hs; p.Wp = Ws; p.B = 1;
-    return halo_eligible(p) ? 1 : 0;
+    return route::halo_eligible_fwd(cin, cout, KH, KW, stride, Hs, Ws, halo_switch().load(std::memory_order_relaxed) != 0) ? 1 : 0;
 }
 
 int gif_conv2d_fwd_f16(const void* big, const void* wp, void* small, const gif_conv_geom* g, const gif_conv_epilogue* e,

@@ -1,7 +1,7 @@
 """-m gpu: every convolution and FIR dispatch route on both sides of its threshold, against an fp64 reference of the same operation.
 
 The rest of the suite picks its shapes by model layer.  Here each row of the tables is a shape computed from a dispatch predicate
-(gif_amd/ops.py: winograd_eligible, x3_conv, x3_tapdense, h2_conv; csrc/conv_igemm.hip: launch(), run_phases, rows_thin_ok,
+(gif_amd/ops.py: winograd_eligible, x3_conv, x3_tapdense, h2_conv; csrc/conv_route.h: route_phase, conv_route, rows_thin_ok,
 halo_eligible; csrc/wgrad_route.h: small_wgrad_ok, wgrad_big_tile, the x3 / x3_thin tile rules of wgrad_route; csrc/elementwise.hip:
 upfirdn2d_impl, gif::reduce_partials): the last shape that takes a route and the first that does not.  Each row's comment names the
 predicate and the side.
@@ -29,8 +29,9 @@ Every case prints its ratio ("[route ratio]" lines with -s) so that a re-measure
 Route assertions, where the library exposes them: ops.prof_read(family) (one record per OP in the family the op ran in: it proves the
 kernel family and contraction mode, not the tile size), ops.prof_winograd_calls(), gif_conv2d_f16_halo_eligible and
 gif_conv2d_x3_eligible.  Tile sizes, the bulk + remainder split and the merged transposed phases are not observable from Python:
-there the row comment is the claim (confirmed by a kernel trace of this module when the tables change).  For the weight gradient the
-claim is checked on the CPU: csrc/wgrad_route.h returns the whole route as a value, tests/test_wgrad_route.py holds its table."""
+the row comment is the claim, and it is checked on the CPU.  csrc/conv_route.h (fwd / dgrad) and csrc/wgrad_route.h (weight gradient)
+return the whole route as a value; tests/test_conv_route.py restates the fwd / dgrad comments as data (CLAIMS) and holds the route table
+to them, tests/test_wgrad_route.py holds the weight gradient's table."""
 import math
 import zlib
 from typing import NamedTuple, Optional
@@ -79,7 +80,9 @@ def _dev(x, c, dtype):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# Convolution route table
+# Convolution route table.  The tile, launch-count, bulk-row and merge claims of the fwd / dgrad row comments are asserted by
+# tests/test_conv_route.py (CLAIMS) against csrc/conv_route.h; tests/golden/conv_route_cases.txt lists these rows' library calls
+# (tests/golden/make_conv_route_cases.py rewrites it when a row changes).
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Kernel families (include/gif_hip.h, gif_prof_read): the family each mode's op must land in.
 DIRECT = {"f16x2": 13, "bf16x3": 8, "native": 0}          # LDS-DMA direct kernels (contraction >= 24 in the split modes, >= 32 native)
