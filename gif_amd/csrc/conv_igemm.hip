@@ -32,22 +32,6 @@
 #include "common.h"
 #include "conv_route.h"
 
-#ifdef GIF_X3_TIMING_PROBE
-// tools/probes/x3_sync_probe.sh: cycles the waves of the bf16x3 direct kernel spend at the mid-stage sync (own DMA wait, barrier), cycles in the K loop, waves
-// [4] / [5]: cycles from kernel entry to the K loop (index tables, ring fill, first split) / from the K loop's end to the kernel's end (epilogue)
-// [6] scale-back + guard, [7] accumulators -> LDS incl. barriers, [8] entry -> first DMA issue (index tables), [9] first issue -> ring filled
-__device__ unsigned long long g_x3_probe[12];
-extern "C" int gif_debug_x3_probe_read(unsigned long long* out8, int reset) {
-    hipDeviceSynchronize();
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_x3_probe), 96) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_x3_probe), z, 96) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -100,7 +84,6 @@ struct GatherParams {
     int pair;                  // f16 kernels, Ci <= 32 (CP == 32): one 64-half K chunk = the channels of TWO taps (see glds_body)
     int dense;                 // bf16x3 kernels, 8 <= Ci < 32, 3x3: 16-byte chunks per tap (Ci / 4) of the tap-dense K order, else 0
     int t2_tx, t2_ty;          // halo kernel: 16 x 16-pixel patches per row / column of the output sub-grid
-    int halo_dbg;              // halo kernel: ablation bits of the probe (GIF_HALO_DBG; results are wrong when set)
 };
 
 // XCD-aware, bijective block remap (cdna guide T1): consecutive logical tiles share an XCD's L2.
@@ -151,20 +134,6 @@ __device__ __forceinline__ void conv_epilogue(const GatherParams& p, f32x16 (&ac
     const T* const msk = static_cast<const T*>(p.mask_src);
     const T* const dsrc = static_cast<const T*>(p.dot_src);
     const bool fused = msk || dsrc || p.part_cs || p.part_dot;  // workgroup-uniform
-#if defined(GIF_EPI_PROBE) && GIF_EPI_PROBE == 3  // timing probe (tools/probes/epilogue_probe.sh; results are WRONG): NO epilogue — every lane
-    // stores the sum of its accumulators, one dword (keeps the K loop alive): the bound for any epilogue rewrite
-    {
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-        if (m0 + wm0 < p.M) yout[(size_t)(m0 + wm0) * p.Co + n0 + wn0 + (tid & 63)] = (T)sacc;
-        return;
-    }
-#endif
     float4 cs = make_float4(0.f, 0.f, 0.f, 0.f), ds = make_float4(0.f, 0.f, 0.f, 0.f);
     // demodulation factors of this lane's four columns: a tile rarely spans more than two samples, so the first sample's and its successor's
     // are loaded once (the row loop loaded them per row and waited for each: +11k cycles per tile on the generator's modulated convs)
@@ -179,9 +148,6 @@ __device__ __forceinline__ void conv_epilogue(const GatherParams& p, f32x16 (&ac
     }
 #pragma unroll
     for (int c = 0; c < EPI_CHUNKS; ++c) {
-#ifdef GIF_X3_TIMING_PROBE
-        const long long probe_c0 = clock64();
-#endif
         __syncthreads();  // staging buffers (c == 0) / previous chunk fully consumed
         if (tid < CR) {  // row table of this chunk
             int b, oy, ox;
@@ -214,9 +180,6 @@ __device__ __forceinline__ void conv_epilogue(const GatherParams& p, f32x16 (&ac
                 }
         }
         __syncthreads();
-#ifdef GIF_X3_TIMING_PROBE
-        if ((tid & 63) == 0) atomicAdd(&g_x3_probe[7], (unsigned long long)(clock64() - probe_c0));
-#endif
         if (n < p.Co) {
             // two copies of the row loop: the plain one carries none of the gradient-producer work (measured on the f16 step, whose
             // MFMA phase is 8x shorter: the extra branches and the running sums cost 2 % of the whole step when they ran always)
@@ -289,9 +252,6 @@ __device__ __forceinline__ void conv_epilogue(const GatherParams& p, f32x16 (&ac
                             }
                             cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
                         }
-#ifdef GIF_NOSTORE_PROBE  // timing probe (tools/probes/epilogue_probe.sh; results are WRONG): the row loop without its global stores
-                        if (p.M < 0)
-#endif
                         {
                             if (sizeof(T) == 2 && p.out_f32) gif::store4(static_cast<float*>(p.y) + off[k], v);
                             else gif::store4_flag(yout + off[k], v, p.sat_flag);
@@ -568,18 +528,6 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             if (bid == 0 && threadIdx.x == 0 && p.h2_stats && p.m_begin == 0) atomicAdd(p.h2_stats, 1u);  // (not the remainder launch)
         }
     }
-#ifdef GIF_DEPHASE_PROBE  // timing probe (tools/probes/dephase_probe.sh): the first round of workgroups starts in GIF_DEPHASE_PROBE phases, a K loop's
-    // 1/PHASES apart on neighbouring CUs of an XCD — do the launch-wide bursts of ring fills and tile stores (every CU at once) cost time?
-    if (X3 == 2 && bid < 256) {
-        const int ph = (bid >> 3) % GIF_DEPHASE_PROBE;
-        const long long d = (long long)(p.ntaps * (p.CP / BK)) * 4300 * ph / GIF_DEPHASE_PROBE, t0 = clock64();
-        while (clock64() - t0 < d) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
-#ifdef GIF_X3_TIMING_PROBE
-    const long long probe_entry = clock64();
-    long long probe_loop_end = probe_entry;
-#endif
     extern __shared__ __attribute__((aligned(16))) float smem[];
     T* As = reinterpret_cast<T*>(smem);  // [NST][BM][LD]
     T* Bs = As + NST * BM * LD;          // [NST][BN][LD]
@@ -770,9 +718,6 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             const int dy = p.dy0 + ta * p.ddy, dx = p.dx0 + tb * p.ddx;
             const unsigned tap_bytes = (unsigned)((dy * p.Wi + dx) * p.Ci + ch - min_off) * 4u;  // this LANE's tap (garbage past the last tap: masked)
             T* Ad = As + buf * BM * LD + wave * RPW * LD;
-#ifdef GIF_KXSHARE_PROBE  // (timing probe, results wrong: activation pieces on every third K step only)
-            if (ld_a % 3 == 0)
-#endif
 #pragma unroll
             for (int it = 0; it < A_IT; ++it) {
                 const unsigned voff = (a_voff[it] + tap_bytes) | (__builtin_amdgcn_ubfe(a_mask[it], (unsigned)t, 1u) - 1u);
@@ -806,10 +751,6 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             const unsigned t_cur = (unsigned)(ld_a * p.nkx + ld_b);            // wave-uniform
             const int so_a = (tap_off - min_off) * 4;                            // >= 0, wave-uniform
             const unsigned ch_or = ch_ok ? 0u : 0xFFFFFFFFu;
-#ifdef GIF_KXSHARE_PROBE  // timing probe (tools/probes/kxshare_probe.sh; results are WRONG): the activation tile is staged for the first
-            // tap of a kernel row only — what staging a row + halo ONCE for its three kx taps would issue
-            if (ld_b == 0)
-#endif
 #pragma unroll
             for (int it = 0; it < A_IT; ++it) {
                 const unsigned voff = a_voff[it] | (__builtin_amdgcn_ubfe(a_mask[it], t_cur, 1u) - 1u) | ch_or;
@@ -857,42 +798,6 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
         if (ld_kc >= p.CP) {
             ld_kc = 0;
             if (++ld_b == p.nkx) { ld_b = 0; ++ld_a; }
-        }
-    };
-
-    // GIF_DMA_SPREAD (probe build, tools/probes/dma_spread_probe.sh): the stage's DMA pieces of the bf16x3 / f16x2 tap-grid order are issued
-    // ONE AT A TIME between the MFMAs of the step's first k-group instead of back to back ahead of it (the microarchitecture guide prices a
-    // piece at ~60 cycles among bare MFMAs and 100-185 inside a phase that already carries pieces and operand reads).  sp_begin fixes the
-    // stage's wave-uniform offsets, sp_piece(k) issues piece k (A pieces first), sp_end advances the K counters.
-    int sp_buf = 0, sp_so_a = 0, sp_so_b = 0;
-    unsigned sp_t = 0, sp_chor = 0;
-    bool sp_on = false;  // wave-uniform: this step has a stage to fetch
-    [[maybe_unused]] auto sp_begin = [&](int buf) __attribute__((always_inline)) {
-        const int dy = p.dy0 + ld_a * p.ddy, dx = p.dx0 + ld_b * p.ddx;
-        const int widx = (p.ky0 + ld_a * p.kstep) * p.KW + p.kx0 + ld_b * p.kstep;
-        sp_buf = buf;
-        sp_t = (unsigned)(ld_a * p.nkx + ld_b);
-        sp_so_a = ((dy * p.Wi + dx) * p.Ci + ld_kc - min_off) * 4;
-        sp_chor = (ld_kc + src_c4 < p.Ci) ? 0u : 0xFFFFFFFFu;
-        sp_so_b = (widx * NPL * p.RP * p.CP + ld_kc) * 2;
-        ld_kc += BK;
-        if (ld_kc >= p.CP) {
-            ld_kc = 0;
-            if (++ld_b == p.nkx) { ld_b = 0; ++ld_a; }
-        }
-    };
-    [[maybe_unused]] auto sp_piece = [&](int k) __attribute__((always_inline)) {
-        if constexpr (X3 != 0) {
-            if (k < A_IT) {
-                T* Ad = As + sp_buf * BM * LD + wave * RPW * LD;
-                const unsigned voff = a_voff[k] | (__builtin_amdgcn_ubfe(a_mask[k], sp_t, 1u) - 1u) | sp_chor;
-                buf_load_lds16(rs_a, (lptr_t)(Ad + k * RPP * LD), voff, sp_so_a);
-            } else {
-                const int it = k - A_IT;
-                const int blk = wave + it * NWAVES;  // wave-uniform
-                if (B3_BLK % NWAVES == 0 || blk < B3_BLK)
-                    buf_load_lds16(rs_b, (lptr_t)(B3 + (sp_buf * B3_BLK + blk) * 512), (unsigned)(b3_off[it] * 2), sp_so_b);
-            }
         }
     };
 
@@ -1030,18 +935,13 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
         // sched_barrier(0) after every MFMA and every piece: the compiler keeps exactly this interleave (sched_group_barrier's
         // VALU class also matches MFMAs).
         constexpr int NPROD = H2 ? 3 : 6;
-        constexpr int NPROD_ = NPROD;
         constexpr int LEAD = H2 ? 4 : 6;  // MFMAs ahead of the first piece: they cover the LDS latency of the raw reads
-        constexpr int SP_N = A_IT + B3_IT;                     // DMA pieces per stage and wave
-        [[maybe_unused]] constexpr int SP_EVERY = (NPROD_ * MT * NT) / SP_N > 0 ? (NPROD_ * MT * NT) / SP_N : 1;  // one piece every SP_EVERY MFMAs
-        auto group = [&](int slot, int nslot, auto dma_tag) __attribute__((always_inline)) {
-            [[maybe_unused]] constexpr bool dma = decltype(dma_tag)::value;
+        auto group = [&](int slot, int nslot) __attribute__((always_inline)) {
             constexpr int TA6[6] = {2, 0, 1, 1, 0, 0}, TB6[6] = {0, 2, 1, 0, 1, 0};
             constexpr int TA3[3] = {1, 0, 0}, TB3[3] = {0, 1, 0};
             int n = 0, piece = H2 ? -1 : 0;  // piece -1: the tracking step of f16x2
-            [[maybe_unused]] int spk = 0;
 #pragma unroll
-            for (int t = (H2 ? 0 : GIF_X3_FIRST_TERM); t < NPROD; ++t)
+            for (int t = 0; t < NPROD; ++t)
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -1056,13 +956,6 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
                                                                                 acc[i][j], 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
                         ++n;
-#ifdef GIF_DMA_SPREAD
-                        if (dma && spk < SP_N && n == 1 + spk * SP_EVERY) {
-                            if (sp_on) sp_piece(spk);
-                            ++spk;
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-#endif
                         if (nslot >= 0 && n >= LEAD && piece < NP) {
                             if (piece < 0) track();
                             else split_piece(nslot, piece);
@@ -1070,13 +963,6 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
-#ifdef GIF_DMA_SPREAD
-            if (dma) {
-#pragma unroll
-                for (; spk < SP_N; ++spk)
-                    if (sp_on) sp_piece(spk);
-            }
-#endif
             if (nslot >= 0) {
 #pragma unroll
                 for (; piece < NP; ++piece) {
@@ -1092,88 +978,32 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
         // DMA instructions per stage and wave (NST == 3: the newest stage stays in flight across the mid-stage sync)
         constexpr int DMA_PER_STAGE = A_IT + B3_IT;
         static_assert(NST == 2 || B3_BLK % NWAVES == 0, "three-stage ring: every wave issues the same number of pieces");
-#ifdef GIF_X3_TIMING_PROBE
-        const long long probe_i0 = clock64();
-#endif
         issue(0);
         if constexpr (NST == 3) {
             if (nsteps > 1) {
                 issue(1);
-#ifndef GIF_NOFILLWAIT_PROBE  // timing probe (tools/probes/epilogue_probe.sh; results are WRONG): the first stage is read before it has landed — what
-                // a first stage prefetched under the PREVIOUS tile's epilogue (a persistent workgroup) would save
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_STAGE) : "memory");
-#endif
             }
         }
-#ifdef GIF_NOFILLWAIT_PROBE
-        if (NST == 3 && nsteps > 1) __builtin_amdgcn_s_barrier();
-        else
-#endif
         __syncthreads();
-#ifdef GIF_X3_TIMING_PROBE
-        if (lane == 0) {
-            atomicAdd(&g_x3_probe[8], (unsigned long long)(probe_i0 - probe_entry));
-            atomicAdd(&g_x3_probe[9], (unsigned long long)(clock64() - probe_i0));
-        }
-#endif
         read_raw(0, 0, 0, 0);
         track();  // (f16x2: first exponents; the accumulators are still zero)
 #pragma unroll
         for (int k = 0; k < NP; ++k) split_piece(0, k);
-#ifdef GIF_X3_TIMING_PROBE
-        long long probe_sync = 0, probe_wait = 0;
-        const long long probe_t0 = clock64();
-#endif
         for (int step = 0; step + 1 < nsteps; ++step) {
-#ifdef GIF_NO_DMA_PROBE  // timing probe (tools/probes/no_dma_probe.sh): the K loop without its LDS-DMA issue — results are WRONG
-            if (step < 1) issue(cur ^ 1);
-#else
-#ifdef GIF_DMA_SPREAD
-            constexpr bool spread = true;  // (probe build: tap-grid launches only; the tap-dense order is NOT handled)
-#else
-            constexpr bool spread = false;
-#endif
             if constexpr (NST == 3) {
                 // stage step + 2 into the buffer of stage step - 1 (its last operand read preceded the previous mid-stage barrier)
-                sp_on = step + 2 < nsteps;
-                if (sp_on) {
-                    if (spread) sp_begin(cur == 0 ? 2 : cur - 1);
-                    else issue(cur == 0 ? 2 : cur - 1);
-                }
+                if (step + 2 < nsteps) issue(cur == 0 ? 2 : cur - 1);
             } else {
-                sp_on = true;
-                if (spread) sp_begin(cur ^ 1);
-                else issue(cur ^ 1);
+                issue(cur ^ 1);
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int g = 0; g + 1 < KG; ++g) {
                 read_raw(cur, g + 1, cmp_kc, (g + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (spread) {
-                    if (g == 0) group(g & 1, (g + 1) & 1, std::true_type{});
-                    else group(g & 1, (g + 1) & 1, std::false_type{});
-                } else {
-                    group(g & 1, (g + 1) & 1, std::false_type{});
-                }
+                group(g & 1, (g + 1) & 1);
             }
-#ifdef GIF_X3_TIMING_PROBE
-            {   // time parked at the mid-stage sync, split into the wave's own DMA wait and the barrier
-                const long long ta = clock64();
-                if (NST == 3 && step + 2 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_STAGE) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const long long tb = clock64();
-                if constexpr (NST == 3) {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                } else {
-                    __syncthreads();
-                }
-                probe_wait += tb - ta;
-                probe_sync += clock64() - tb;
-            }
-#else
             if constexpr (NST == 3) {
                 // stage step + 1 has landed (this wave's pieces; behind the barrier everybody's), stage step + 2 may stay in flight
                 if (step + 2 < nsteps) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(DMA_PER_STAGE) : "memory");
@@ -1182,13 +1012,12 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             } else {
                 __syncthreads();
             }
-#endif
             cmp_kc = next_kc(cmp_kc);
             if constexpr (NST == 3) cur = cur == 2 ? 0 : cur + 1;
             else cur ^= 1;
             read_raw(cur, 0, cmp_kc, 0);
             __builtin_amdgcn_sched_barrier(0);
-            group((KG - 1) & 1, 0, std::false_type{});
+            group((KG - 1) & 1, 0);
         }
 #pragma unroll
         for (int g = 0; g < KG; ++g) {
@@ -1196,18 +1025,8 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
                 read_raw(cur, g + 1, cmp_kc, (g + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            group(g & 1, g + 1 < KG ? (g + 1) & 1 : -1, std::false_type{});
+            group(g & 1, g + 1 < KG ? (g + 1) & 1 : -1);
         }
-#ifdef GIF_X3_TIMING_PROBE
-        if (lane == 0) {
-            atomicAdd(&g_x3_probe[0], (unsigned long long)probe_wait);
-            atomicAdd(&g_x3_probe[1], (unsigned long long)probe_sync);
-            atomicAdd(&g_x3_probe[2], (unsigned long long)(clock64() - probe_t0));
-            atomicAdd(&g_x3_probe[3], 1ull);
-            atomicAdd(&g_x3_probe[4], (unsigned long long)(probe_t0 - probe_entry));
-        }
-        probe_loop_end = clock64();
-#endif
         if constexpr (H2) {
             // guard: a row one of whose 16-element K groups lies more than 2^kH2Window below the row maximum (the group's values no
             // longer carry 22 bits) ...
@@ -1308,13 +1127,7 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
         mfma_group(g & 1);
     }
     }
-#ifdef GIF_X3_TIMING_PROBE
-    if (X3 && lane == 0) atomicAdd(&g_x3_probe[6], (unsigned long long)(clock64() - probe_loop_end));
-#endif
     conv_epilogue<BM, BN, 32, MT, NT, T, THREADS>(p, acc, smem, m0, n0, wm0, wn0, tid, li, lh, HWp);
-#ifdef GIF_X3_TIMING_PROBE
-    if (X3 && lane == 0) atomicAdd(&g_x3_probe[5], (unsigned long long)(clock64() - probe_loop_end));
-#endif
 }
 
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, bool SCALE, int BK, int X3 = 0, int NST = 2>
@@ -1613,11 +1426,10 @@ __global__ void __launch_bounds__(256, 3) conv_halo_f16(const GatherParams p) {
     const int HWh = TW + p.nkx - 1;
     const int nchunks = (TH + p.nky - 1) * HWh * CPP;
     const bool has_scale = p.in_scale != nullptr;
-    const int dbg = p.halo_dbg;  // ablation builds of the probe only (results are wrong): 1 no patch DMA, 2 no taps, 4 no stores
 
     // ---- stage the input patch + halo (one pass, LDS-DMA).  Lane's chunk e = 64 * wave + lane + 256 * it: its physical chunk e % CPP
     // is the same in every pass; its pixel index q advances by 256 / CPP, i.e. (dqy, dqx) in the halo grid (no division per pass).
-    if (!(dbg & 1)) {
+    {
         constexpr int QSTEP = 256 / CPP;
         const int dqy = QSTEP / HWh, dqx = QSTEP - dqy * HWh;  // scalar
         int q = (wave * 64 + lane) >> CPP_SHIFT;
@@ -1705,7 +1517,7 @@ __global__ void __launch_bounds__(256, 3) conv_halo_f16(const GatherParams p) {
     const char* Wb = reinterpret_cast<const char*>(Wsm);
     __syncthreads();  // the workgroup release waits for every wave's outstanding LDS-DMA (patch and weights)
     int ta = 0, tb = 0;  // tap (row, column) of the grid, advanced without divisions
-    for (int t = 0; t < ((dbg & 2) ? 0 : p.ntaps); ++t) {
+    for (int t = 0; t < p.ntaps; ++t) {
         const int off = (p.dy0 + ta * p.ddy - dy_min) * HWh + (p.dx0 + tb * p.ddx - dx_min);  // wave-uniform tap shift
         if (++tb == p.nkx) { tb = 0; ++ta; }
         gif::f16x8_t av[KG][MT], bw[KG][NT];
@@ -1735,7 +1547,6 @@ __global__ void __launch_bounds__(256, 3) conv_halo_f16(const GatherParams p) {
                 for (int j = 0; j < NT; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[kg][i], bw[kg][j], acc[i][j], 0, 0, 0);
     }
-    if (dbg & 4) return;
     conv_epilogue<BM, BN, 8, MT, NT, T, 256, true, halo_lds_floats<BN, CP>()>(p, acc, smem, tile * BM, 0, wave * 64, 0, tid, li, lh, 0, b, tyi * TH, txi * TW);
 }
 
@@ -1758,7 +1569,6 @@ const route::ConvKnobs& conv_knobs() {
         k.x3_multi_big = num("GIF_X3_MULTI_BIG", 1) != 0;
         k.conv_variant = num("GIF_CONV_VARIANT", 0);
         k.f16_halo = num("GIF_F16_HALO", 1) != 0;
-        k.halo_dbg = num("GIF_HALO_DBG", 0);
         return k;
     }();
     return once;
@@ -1900,11 +1710,6 @@ int conv_dispatch(const route::ConvLaunch& l, const GatherParams* ph, hipStream_
             break;
         }
         case route::CONV_HALO:
-#ifdef GIF_HALO_PROBE  // ablation bits of tools/probes (results are wrong when set): never in the production library
-            p.halo_dbg = conv_knobs().halo_dbg;
-#else
-            p.halo_dbg = 0;
-#endif
             launched = halo_try<32, 32>(l, p, s) || halo_try<32, 64>(l, p, s) || halo_try<64, 32>(l, p, s) || halo_try<64, 64>(l, p, s);
             break;
         }

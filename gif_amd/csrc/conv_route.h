@@ -24,7 +24,6 @@ struct ConvKnobs {
     bool x3_multi_big = true;  // GIF_X3_MULTI_BIG: off iff atoi == 0 (merged 256x128 phases of the big transposed convs)
     int conv_variant = 0;      // GIF_CONV_VARIANT: atoi; 1 = register-staged operands, 3 = no 128x128 remainder split, != 0 = no merged phases
     bool f16_halo = true;      // GIF_F16_HALO: atoi != 0; the INITIAL value of the run-time switch gif_conv2d_f16_halo_enable (conv_route's halo_on)
-    int halo_dbg = 0;          // GIF_HALO_DBG: atoi; ablation bits of conv_halo_f16, honoured by builds with GIF_HALO_PROBE only
 };
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

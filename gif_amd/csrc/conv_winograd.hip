@@ -561,9 +561,8 @@ __global__ void __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) wino_gemm_mfma(cons
 // at the end of each position, un-overlapped inside the wave (the SIMD's other wave keeps the matrix pipe busy).
 // Per group: the V fragments of the NEXT group are read first and split piecewise between this group's MFMAs; the weight
 // operands are reloaded term by term as soon as the last MFMA that uses a term has issued (lo after 2, mid after 6, hi after 12).
-// DBG (ablation builds only, GIF_WINO_DBG; results are wrong): 1 = no fold, 2 = no split of V, 4 = no weight-operand reloads
 // Block BM x BN = 128 x 128 (4 x 2 waves; default) or 256 x 64 (8 x 1 waves: every V fragment is split by exactly one wave).
-template <int DBG = 0, int BM = 256, int BN = 64>
+template <int BM = 256, int BN = 64>
 __global__ void __launch_bounds__(512, 1) wino_gemm_x3(const WinoParams p) {
     if (p.gate) {  // guarded fallback of an f16x2 launch: nothing to do unless that launch raised the gate
         if (*p.gate < p.gate_gen) return;
@@ -672,24 +671,24 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_x3(const WinoParams p) {
     auto group = [&](int slot, int rbuf, int nq) __attribute__((always_inline)) {
         read_a(rbuf, nq);
         __builtin_amdgcn_sched_barrier(0);
-        if (GIF_X3_FIRST_TERM == 0) mma(slot, 0, 2);  // hi * lo
-        if (!(DBG & 4)) read_b(rbuf, nq, 2);
+        mma(slot, 0, 2);  // hi * lo
+        read_b(rbuf, nq, 2);
         __builtin_amdgcn_sched_barrier(0);
-        if (GIF_X3_FIRST_TERM == 0) mma(slot, 1, 1);  // mid * mid
-        if (!(DBG & 2)) split_piece(slot ^ 1, 0);
+        mma(slot, 1, 1);  // mid * mid
+        split_piece(slot ^ 1, 0);
         __builtin_amdgcn_sched_barrier(0);
         mma(slot, 0, 1);  // hi * mid
-        if (!(DBG & 4)) read_b(rbuf, nq, 1);
-        if (!(DBG & 2)) split_piece(slot ^ 1, 1);
+        read_b(rbuf, nq, 1);
+        split_piece(slot ^ 1, 1);
         __builtin_amdgcn_sched_barrier(0);
-        if (GIF_X3_FIRST_TERM == 0) mma(slot, 2, 0);  // lo * hi
-        if (!(DBG & 2)) split_piece(slot ^ 1, 2);
+        mma(slot, 2, 0);  // lo * hi
+        split_piece(slot ^ 1, 2);
         __builtin_amdgcn_sched_barrier(0);
         mma(slot, 1, 0);  // mid * hi
-        if (!(DBG & 2)) split_piece(slot ^ 1, 3);
+        split_piece(slot ^ 1, 3);
         __builtin_amdgcn_sched_barrier(0);
         mma(slot, 0, 0);  // hi * hi
-        if (!(DBG & 4)) read_b(rbuf, nq, 0);
+        read_b(rbuf, nq, 0);
         __builtin_amdgcn_sched_barrier(0);
     };
     auto fold = [&](int pos) __attribute__((always_inline)) {
@@ -738,12 +737,11 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_x3(const WinoParams p) {
         cur = cur == 2 ? 0 : cur + 1;
         group(1, cur, 0);  // (after the last stage this prepares operands nobody uses: the reads stay inside the ring)
         if (++kc_in_pos == kchunks) {
-            if (!(DBG & 1)) fold(pos);
+            fold(pos);
             kc_in_pos = 0;
             ++pos;
         }
     }
-    if (DBG & 1) fold(5);
 
     // ---- epilogue: for each output position (a,b): transpose through LDS, then coalesced float4 rows
     constexpr int LDC = BN + 4;
@@ -822,13 +820,7 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_h2(const WinoParams p) {
         b2_off[it] = (unsigned)((size_t)term * planeU + (size_t)(n0 + r) * p.CP + (((lane & 3) ^ ((lane >> 4) & 3)) << 3));
     }
     const int kchunks = p.CP / WBK;
-#ifdef GIF_WINO_F4_PROBE  // timing probe (tools/probes/wino_f4_probe.py; results are meaningless): the GEMM of an UNFUSED F(4x4,3x3) — 36
-    // position GEMMs over a quarter of the rows, every position's accumulator stored as its own M plane (through p.residual) instead of
-    // being folded into 2x2 outputs; no output transform, no epilogue
-    const int nsteps = 36 * kchunks;
-#else
     const int nsteps = 16 * kchunks;
-#endif
     const float* vptr = p.V;
     const unsigned short* uptr = U2;
     int ld_kc = 0;
@@ -993,30 +985,11 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_h2(const WinoParams p) {
         cur = cur == NST - 1 ? 0 : cur + 1;
         group(1, cur, 0);  // (after the last stage this prepares operands nobody uses: the reads stay inside the ring)
         if (++kc_in_pos == kchunks) {
-#ifdef GIF_WINO_F4_PROBE
-            {
-                float* Mp = const_cast<float*>(p.residual) + (size_t)pos * p.ntiles_pad * p.RP;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const int er = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_ex);
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        Mp[(size_t)row * p.RP + n0 + wn0 + j * 32 + li] = ldexpf(acc[j][r], -er);
-                        acc[j][r] = 0.f;
-                    }
-                }
-            }
-#else
             fold(pos);
-#endif
             kc_in_pos = 0;
             ++pos;
         }
     }
-#ifdef GIF_WINO_F4_PROBE
-    return;
-#endif
 
     // guard (common.h): a 16-element K group more than 2^kH2Window below its row's maximum meeting a weight row the packing flagged
     // raises the launch's gate
@@ -1434,7 +1407,6 @@ static int conv3x3_winograd_x3_impl(const float* x, const void* U2, const void* 
     p.gain = e ? e->gain : 1.f;
     p.B = B; p.H = H; p.W = W; p.Co = Co;
     p.ntiles = (int)ntiles; p.ntiles_pad = (int)ntiles_pad; p.TH = H / 2; p.TW = W / 2;
-    static const int dbg = gif::knob("GIF_WINO_DBG") ? atoi(gif::knob("GIF_WINO_DBG")) : 0;
     // 128 x 128 blocks (4 x 2 waves) by default; GIF_WINO_X3_TILE=256 selects 256 x 64 (8 x 1 waves: every V fragment split
     // once instead of twice) — measured equal (2.998 / 2.141 / 1.790 ms vs 2.993 / 2.133 / 1.757 ms on the three big layers)
     static const int sq = gif::knob("GIF_WINO_X3_TILE") ? atoi(gif::knob("GIF_WINO_X3_TILE")) != 256 : 1;
@@ -1476,18 +1448,14 @@ static int conv3x3_winograd_x3_impl(const float* x, const void* U2, const void* 
         }
         p.gate = q.gate; p.gate_gen = q.gate_gen; p.h2_stats = gif::h2_stats_words();
     }
-#define GIF_WINO_X3_LAUNCH(D, BM_, BN_)                                                        \
-    {                                                                                          \
-        static gif::LdsAttr attr;                                                              \
-        attr.ensure(reinterpret_cast<const void*>(wino_gemm_x3<D, BM_, BN_>), lds);            \
-        hipLaunchKernelGGL((wino_gemm_x3<D, BM_, BN_>), grid, dim3(512), lds, s, p);           \
+#define GIF_WINO_X3_LAUNCH(BM_, BN_)                                                      \
+    {                                                                                     \
+        static gif::LdsAttr attr;                                                         \
+        attr.ensure(reinterpret_cast<const void*>(wino_gemm_x3<BM_, BN_>), lds);          \
+        hipLaunchKernelGGL((wino_gemm_x3<BM_, BN_>), grid, dim3(512), lds, s, p);         \
     }
-    if (!sq && !U2) GIF_WINO_X3_LAUNCH(0, 256, 64)
-    else if (dbg == 1) GIF_WINO_X3_LAUNCH(1, 128, 128)
-    else if (dbg == 2) GIF_WINO_X3_LAUNCH(2, 128, 128)
-    else if (dbg == 4) GIF_WINO_X3_LAUNCH(4, 128, 128)
-    else if (dbg == 7) GIF_WINO_X3_LAUNCH(7, 128, 128)
-    else GIF_WINO_X3_LAUNCH(0, 128, 128)
+    if (!sq && !U2) GIF_WINO_X3_LAUNCH(256, 64)
+    else GIF_WINO_X3_LAUNCH(128, 128)
 #undef GIF_WINO_X3_LAUNCH
     if (int rc = sums.finish(p, B, H, W, Co, bm, s)) return rc;
     return gif::check_launch("conv3x3_winograd_f32x3");

@@ -5,8 +5,8 @@
 // modes, and with shape.planes the 16 plane GEMMs of the Winograd weight gradient), wgrad_route_f16 (f16 operands) — and launches what
 // the returned value names; the splits queries ask wgrad_splits / wgrad_splits_f16.  Nothing else in the library decides a weight-
 // gradient tile, stage depth, twin or profiling family.  NOT modelled here, because they depend on the filled kernel parameters or on
-// a build flag and sit next to the launch: the buffer-addressed / register-prefetch forms of conv_wgrad_h2v2 (h2v2_buf_ok, h2v3_ok:
-// GIF_H2_WGRAD_BUF, GIF_H2_WGRAD_V3), the GIF_WGRAD_KX3_PROBE blocks, and GIF_H2_GUARD=0 (no gate: the guarded twin is not launched).
+// run-time state and sit next to the launch: the buffer-addressed form of conv_wgrad_h2v2 (h2v2_buf_ok: GIF_H2_WGRAD_BUF) and
+// GIF_H2_GUARD=0 (no gate: the guarded twin is not launched).
 #pragma once
 #include <stddef.h>
 

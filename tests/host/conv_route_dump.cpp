@@ -229,7 +229,6 @@ int main(int argc, char** argv) {
     with("GIF_CONV_VARIANT=2", [](ConvKnobs& k) { k.conv_variant = 2; });
     with("GIF_CONV_VARIANT=3", [](ConvKnobs& k) { k.conv_variant = 3; });
     with("GIF_F16_HALO=0", [](ConvKnobs& k) { k.f16_halo = false; }, false);  // (the switch's initial value: conv_route's halo_on)
-    with("GIF_HALO_DBG=7", [](ConvKnobs& k) { k.halo_dbg = 7; });            // (a kernel argument of probe builds: no route changes)
     for (const Setting& st : settings) {
         int differ = 0;
         for (const Case& c : g) {

@@ -49,7 +49,7 @@ def test_route_table_matches_the_recorded_one(dump_lines):
     for i, (a, b) in enumerate(zip(dump_lines, want)):
         assert a == b, f"line {i + 1}:\n got  {a}\n want {b}"
     assert len(dump_lines) == len(want)
-    assert 300 < len(want) < 500 and sum("differ from the default" in l for l in want) == 12
+    assert 300 < len(want) < 500 and sum("differ from the default" in l for l in want) == 11
 
 
 def test_case_file_is_current():

@@ -7,13 +7,7 @@
 set -eu
 cd "$(dirname "$0")/../.."
 if [ "$1" = build ]; then
-  make -s -j8 -C gif_amd/csrc ARCH=gfx950
-  cd gif_amd/csrc; mkdir -p _probe
-  for n in 2 4; do
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wno-unused-function -DGIF_DEPHASE_PROBE=$n -c conv_igemm.hip -o _probe/conv_igemm_dephase$n.o &
-  done; wait
-  OBJS=$(ls _build/*.o | grep -v "conv_igemm.o")
-  for n in 2 4; do /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgif_hip_dephase$n.so $OBJS _probe/conv_igemm_dephase$n.o; done
+  for n in 2 4; do bash tools/probes/probe_lib.sh dephase$n "-DGIF_DEPHASE_PROBE=$n" conv_igemm; done
 else
   cp gif_amd/libgif_hip.so /tmp/keep.so
   echo "== normal library"; python tools/probes/kxshare_probe.py

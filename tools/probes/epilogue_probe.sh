@@ -9,14 +9,7 @@ set -eu
 cd "$(dirname "$0")/../.."
 VARIANTS="nostore:-DGIF_NOSTORE_PROBE noepi:-DGIF_EPI_PROBE=3 nofillwait:-DGIF_NOFILLWAIT_PROBE"
 if [ "$1" = build ]; then
-  make -s -j8 -C gif_amd/csrc ARCH=gfx950
-  cd gif_amd/csrc; mkdir -p _probe
-  for v in $VARIANTS; do
-    n=${v%%:*}; f=$(echo ${v#*:} | tr ',' ' ')
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wno-unused-function -Wno-unused-value $f -c conv_igemm.hip -o _probe/conv_igemm_$n.o &
-  done; wait
-  OBJS=$(ls _build/*.o | grep -v "conv_igemm.o")
-  for v in $VARIANTS; do n=${v%%:*}; /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgif_hip_$n.so $OBJS _probe/conv_igemm_$n.o; done
+  for v in $VARIANTS; do bash tools/probes/probe_lib.sh ${v%%:*} "${v#*:}" conv_igemm; done
 else
   cp gif_amd/libgif_hip.so /tmp/keep.so
   echo "== normal library"; python tools/probes/kxshare_probe.py

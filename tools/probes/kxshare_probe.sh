@@ -7,11 +7,7 @@
 set -eu
 cd "$(dirname "$0")/../.."
 if [ "$1" = build ]; then
-  make -s -j8 -C gif_amd/csrc ARCH=gfx950
-  cd gif_amd/csrc; mkdir -p _probe
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wno-unused-function -DGIF_KXSHARE_PROBE -c conv_igemm.hip -o _probe/conv_igemm_kxshare.o
-  OBJS=$(ls _build/*.o | grep -v "conv_igemm.o")
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgif_hip_kxshare.so $OBJS _probe/conv_igemm_kxshare.o
+  bash tools/probes/probe_lib.sh kxshare "-DGIF_KXSHARE_PROBE" conv_igemm
 else
   echo "== normal library"; python tools/probes/kxshare_probe.py
   cp gif_amd/libgif_hip.so /tmp/keep.so; cp gif_amd/libgif_hip_kxshare.so gif_amd/libgif_hip.so

@@ -6,11 +6,7 @@
 set -eu
 cd "$(dirname "$0")/../.."
 if [ "$1" = build ]; then
-  make -s -j8 -C gif_amd/csrc ARCH=gfx950
-  cd gif_amd/csrc; mkdir -p _probe
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wno-unused-function -DGIF_WGRAD_KX3_PROBE -c conv_wgrad.hip -o _probe/conv_wgrad_kx3.o
-  OBJS=$(ls _build/*.o | grep -v "conv_wgrad.o")
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgif_hip_wgkx3.so $OBJS _probe/conv_wgrad_kx3.o
+  bash tools/probes/probe_lib.sh wgkx3 "-DGIF_WGRAD_KX3_PROBE" conv_wgrad
 else
   cp gif_amd/libgif_hip.so /tmp/keep.so
   echo "== normal library"; python tools/probes/wgrad_buf_probe.py child

@@ -3,11 +3,7 @@
 set -eu
 cd "$(dirname "$0")/../.."
 if [ "$1" = build ]; then
-  make -s -j8 -C gif_amd/csrc ARCH=gfx950
-  cd gif_amd/csrc; mkdir -p _probe
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wno-unused-function -DGIF_WINO_F4_PROBE -c conv_winograd.hip -o _probe/conv_winograd_f4.o
-  OBJS=$(ls _build/*.o | grep -v "conv_winograd.o")
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgif_hip_f4probe.so $OBJS _probe/conv_winograd_f4.o
+  bash tools/probes/probe_lib.sh f4probe "-DGIF_WINO_F4_PROBE" conv_winograd
 else
   echo "== today: F(2x2,3x3), fused output transform + epilogue"; python tools/probes/wino_f4_probe.py
   cp gif_amd/libgif_hip.so /tmp/keep.so; cp gif_amd/libgif_hip_f4probe.so gif_amd/libgif_hip.so

@@ -1,5 +1,7 @@
 """Times wino_gemm_x3 alone (the input transform is timed separately and subtracted) on the benchmark's Winograd layers.
-GIF_WINO_DBG selects an ablation build of the kernel (wrong results, see conv_winograd.hip)."""
+GIF_WINO_DBG (with GIF_EXPERIMENTAL=1) selects an ablation instantiation of the kernel (wrong results).  Those instantiations are not in
+gif_amd/csrc: they are tools/probes/ablation_knobs.patch, and  bash tools/probes/probe_lib.sh winodbg "" conv_winograd  builds
+gif_amd/libgif_hip_winodbg.so with them (swap it in for the run, as the *_probe.sh scripts do)."""
 import os
 import sys
 

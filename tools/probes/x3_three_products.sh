@@ -7,13 +7,7 @@
 set -eu
 cd "$(dirname "$0")/../.."
 if [ "$1" = build ]; then
-  make -s -j8 -C gif_amd/csrc ARCH=gfx950
-  cd gif_amd/csrc; mkdir -p _probe
-  for f in conv_igemm conv_wgrad conv_winograd; do
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wno-unused-function -DGIF_X3_FIRST_TERM=3 -c $f.hip -o _probe/$f.o &
-  done; wait
-  OBJS=$(ls _build/*.o | grep -v "conv_igemm.o\|conv_wgrad.o\|conv_winograd.o")
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgif_hip_probe3.so $OBJS _probe/conv_igemm.o _probe/conv_wgrad.o _probe/conv_winograd.o
+  bash tools/probes/probe_lib.sh probe3 "-DGIF_X3_FIRST_TERM=3" conv_igemm conv_wgrad conv_winograd
 else
   O=$2; mkdir -p $O
   B="python bench.py --no-cpu-baseline --no-prof --steps 12 --warmup 3"
