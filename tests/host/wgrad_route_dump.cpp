@@ -2,9 +2,11 @@
 // One line per case:
 //   geometry | mode | u(nscaled) / s(caled) | nsplit -> primary launch [+ twin] ; route fields | tiles per split, splits of the query
 // first over a fixed grid with the default knobs, then once per non-default knob value over a smaller grid, where only the cases are
-// printed whose line differs from the default one (and how many of how many did).  tests/test_wgrad_route.py builds this with
+// printed whose line differs from the default one (and how many of how many did).  With arguments: the lines of the plane GEMMs asked
+// for (see main).  tests/test_wgrad_route.py builds this with
 // AddressSanitizer and UBSan (host code only), runs it and compares the output with tests/golden/wgrad_route_table.txt line by line.
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -147,8 +149,20 @@ std::vector<Case> knob_grid() {
 
 }  // namespace
 
-int main() {
+// `planes <ntiles> <CsP> <CbP> <mode> <nsplit>` (any number of such groups): one line per group for the plane GEMMs of that Winograd
+// weight gradient instead of the table (tests/test_cpu_wiring.py asks for the rows of tests/test_gpu_winograd_edges.py this way)
+int main(int argc, char** argv) {
     const WgradKnobs def;
+    if (argc > 1) {
+        if ((argc - 1) % 6 != 0) return 2;
+        for (int i = 1; i < argc; i += 6) {
+            if (strcmp(argv[i], "planes") != 0) return 2;
+            const int mode = atoi(argv[i + 4]);
+            if (mode < 0 || mode > 2) return 2;
+            puts(line(planes(atol(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3])), mode, atoi(argv[i + 5]), def).c_str());
+        }
+        return 0;
+    }
     for (const Case& c : full_grid()) puts(line(c.g, c.mode, c.nsplit, def).c_str());
 
     struct Setting {

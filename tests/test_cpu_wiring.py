@@ -661,3 +661,150 @@ def test_pointwise_edges_fir_rows_match_the_oracle():
         assert torch.equal(pos > 0, P.fir_support(row)), name
         if flip is False and KH * KW > 1:
             assert (got - P.fir64(x, k, up, down, pad0, (Ho, Wo), True)).abs().max() > 1e-3, f"{name}: the kernel is symmetric"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tests/test_gpu_winograd_edges.py: the edge each row claims, recomputed from the constants of csrc/conv_winograd.hip and from
+# csrc/wgrad_route.h (through tests/host/wgrad_route_dump.cpp), and its fp64 restatements tied to ATen float64.  No GPU.
+# ---------------------------------------------------------------------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _winograd():
+    import test_gpu_winograd_edges as WE
+    return WE
+
+
+def test_winograd_edges_constants_are_the_sources():
+    """A constant changed in conv_winograd.hip fails here; it does not silently move a row off its edge."""
+    import re
+    WE = _winograd()
+    with open(os.path.join(ROOT, "gif_amd", "csrc", "conv_winograd.hip")) as f:
+        src = f.read()
+
+    def one(pattern):
+        m = re.findall(pattern, src)
+        assert len(m) == 1, (pattern, m)
+        return m[0]
+
+    wbm, wbn, wbk = map(int, one(r"constexpr int WBM = (\d+), WBN = (\d+), WBK = (\d+), WNSTAGE = 3;"))
+    a, b, c, d = map(int, one(r"if \(blocks > (\d+) \* (\d+)\) blocks = (\d+) \* (\d+);"))
+    assert (a, b) == (c, d)
+    got = dict(WBM=wbm, WBN=wbn, WBK=wbk, WPAD=int(one(r"constexpr int WPAD = (\d+);")), CAP_WG=a * b,
+               TYB=int(one(r"if \(!e\) return (\d+);\n\s+return !strncmp\(e, \"rows\", 4\)")),
+               WIDE_MIN=int(one(r"\(Co % 128 == 0 && \(long\)p\.tiles_m \* \(p\.RP / 128\) >= (\d+)\)")))
+    assert got == WE.K
+    # the expressions geometry() restates
+    one(r"const long lanes = \(long\)B \* \(\(H / 2 \+ rows - 1\) / rows\) \* \(W / 2\) \* \(CP / 4\);")
+    one(r"long blocks = \(total \+ 255\) / 256;")
+    one(r"p\.tiles_m = \(int\)\(ntiles_pad / WBM\);")
+    one(r"const int bm = \(sq \|\| U2\) \? 128 : 256, bn = \(sq \|\| U2\) \? 128 : 64;")
+    assert len(re.findall(r"for \(unsigned idx = blockIdx\.x \* blockDim\.x \+ threadIdx\.x; idx < [^;]+; idx \+= gridDim\.x \* blockDim\.x\)", src)) == 3
+    assert WE.CAP_LANES == 2097152 == 32 * 16 * 128 * 32  # the benchmark's own shape: batch 32, 256^2, 128 channels
+
+
+def test_winograd_edges_forward_rows_sit_on_their_edges():
+    from gif_amd import _lib
+    import ctypes
+    WE = _winograd()
+    lib = _lib.load()
+    names = [r.name for r in WE.FROWS]
+    assert len(set(names)) == len(names)
+    seen = set()
+    for row in WE.FROWS:
+        B, C, Co, H, W = row.shape
+        assert H % 2 == 0 and W % 2 == 0 and C % 4 == 0 and Co % 4 == 0 and row.claim
+        for mode in WE.MODES:
+            geo = WE.geometry(*row.shape, mode)
+            rp, cp = ctypes.c_int(), ctypes.c_int()
+            dims = lib.gif_winograd_pack_dims_x3 if geo["gemm"] in ("x3", "h2") else lib.gif_winograd_pack_dims
+            assert dims(Co, C, ctypes.byref(rp), ctypes.byref(cp)) == 0 and (rp.value, cp.value) == (geo["RP"], geo["CP"]), row.name
+            assert lib.gif_winograd_workspace_floats(B, H, W, C) == 16 * geo["ntiles_pad"] * geo["CP"], row.name
+            assert geo["ntiles_pad"] * geo["CP"] < 2 ** 31 and B * H * W * max(C, Co) < 2 ** 31, row.name  # the library's own limits
+            for key, want in row.claim.items():
+                k, _, m = key.partition(":")
+                if (m or "native") == mode:
+                    assert geo[k] == want, (row.name, mode, k, geo[k], want)
+                    seen.add(k)
+        if row.epi == "fusedot":
+            assert (H // 2) * (W // 2) % 128 == 0
+    assert seen >= {"ntiles", "ntiles_pad", "lanes", "trips", "tiles_m", "wide", "RP", "CP", "nwg", "gemm", "yblocks", "last_block", "pad_blocks"}
+    by = {r.name: WE.geometry(*r.shape) for r in WE.FROWS}
+    assert by["cap_exact"]["lanes"] == WE.CAP_LANES and by["cap_over"]["lanes"] - WE.CAP_LANES == by["cap_over"]["CP"] // 4  # exactly one tile
+    assert {by[n]["ntiles"] for n in ("t127", "t128", "t129", "t255", "t256", "t257")} == {127, 128, 129, 255, 256, 257}
+    assert all(g["tiles_m"] % 2 == 0 for g in by.values())  # WPAD = 2 * WBM: an odd workgroup count such as 9 cannot occur
+    assert {by[n]["nwg"] % 8 for n in ("t127", "nwg6", "nwg10")} == {2, 6} and by["nwg10"]["nwg"] > 8
+
+
+def test_winograd_edges_wgrad_rows_sit_on_their_edges(tmp_path):
+    """Tile pair, 256-row tile, bf16x3 / f16x2 eligibility, split count and chunk of every weight-gradient row, from wgrad_route.h."""
+    import re
+    import subprocess
+    from gif_amd import _lib
+    WE = _winograd()
+    lib = _lib.load()
+    exe = str(tmp_path / "wgrad_route_dump")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    flags = "-x c++ -std=c++17 -O1 -g -Wall -Werror -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
+    built = subprocess.run([hipcc] + flags.split() + ["-I", os.path.join(ROOT, "gif_amd", "csrc"),
+                                                      os.path.join(ROOT, "tests", "host", "wgrad_route_dump.cpp"), "-o", exe],
+                           capture_output=True, text=True, timeout=600)
+    assert built.returncode == 0, built.stderr[-4000:]
+    pad32 = lambda c: (c + 31) // 32 * 32
+    cases, args = [], []
+    for row in WE.WROWS:
+        B, Cs, Cb, H, W, O, I = row.shape
+        assert O <= Cs and I <= Cb and Cs % 4 == 0 and Cb % 4 == 0 and H % 2 == 0 and W % 2 == 0
+        ntiles = B * (H // 2) * (W // 2)
+        assert ntiles == row.claim["ntiles"]
+        nsplit = lib.gif_conv3x3_winograd_wgrad_splits(B, H, W, Cs, Cb)
+        for mode in row.modes:
+            cases.append((row, mode, nsplit))
+            args += ["planes", str(ntiles), str(pad32(Cs)), str(pad32(Cb)), str(WE.MODES.index(mode)), str(nsplit)]
+    ran = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300)
+    assert ran.returncode == 0, (ran.returncode, ran.stderr[-4000:])
+    lines = ran.stdout.splitlines()
+    assert len(lines) == len(cases)
+    pat = re.compile(r"-> (?:mfma f32 (\d+)x(\d+) \S+ \S+ bkp(\d+) tab0 x3=(\d)|h2v2 tab1) thr256|-> mfma f32 32x32 w1x1 glds1 bkp32 tab0 x3=0 thr64")
+    seen_tiles, multi_short = set(), False
+    for (row, mode, nsplit), l in zip(cases, lines):
+        c = row.claim
+        chunk, fam, splits = (int(re.search(p, l).group(1)) for p in (r" chunk(\d+) ", r" fam(\d+) ", r" splits (\d+)$"))
+        assert splits == nsplit == c.get("nsplit", nsplit), (row.name, l)  # the header's count is the library's
+        assert chunk == c.get("chunk", chunk) and chunk % 32 == 0 and (nsplit - 1) * chunk < c["ntiles"] <= nsplit * chunk, (row.name, l)
+        multi_short |= nsplit > 1 and nsplit * chunk > c["ntiles"]
+        native_tile = re.search(r"mfma f32 (\d+)x(\d+) ", l)
+        x3 = mode != "native" and bool(c.get("x3"))
+        assert fam == (3 if not x3 else 11 if mode == "bf16x3" else 16), (row.name, mode, l)
+        if mode == "native":
+            assert (int(native_tile.group(1)), int(native_tile.group(2))) == c["tile"], (row.name, l)
+            assert ("256x128" in l) == bool(c.get("big")), (row.name, l)
+            seen_tiles.add(c["tile"])
+        elif x3:
+            assert c["tile"] == (128, 128) and ("x3=1" in l) and (mode == "bf16x3" or l.split("->")[1].lstrip().startswith("h2v2")), (row.name, l)
+        else:
+            assert "x3=0" in l and "twin" not in l, (row.name, l)
+    assert seen_tiles == {(32, 32), (32, 128), (128, 32), (128, 128), (256, 128)} and multi_short
+    assert {r.claim["ntiles"] for r in WE.WROWS} >= {31, 33, 75, 129, 16384, 16128}
+
+
+def test_winograd_edges_restatements():
+    """wino_v64, the V reference: folded with G g G^T through A^T . A (F(2x2, 3x3)) it is the convolution in ATen float64, which ties
+    its position and tile order to the operation; the data gradient as a forward conv with flipped taps and swapped channels."""
+    WE = _winograd()
+    G = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64)
+    AT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float64)
+    g = torch.Generator().manual_seed(11)
+    for B, C, O, H, W in ((2, 5, 3, 2, 2), (1, 4, 6, 6, 4), (3, 3, 2, 4, 10)):
+        x = torch.randn(B, C, H, W, generator=g, dtype=torch.float64)
+        w = torch.randn(O, C, 3, 3, generator=g, dtype=torch.float64)
+        gy = torch.randn(B, O, H, W, generator=g, dtype=torch.float64)
+        V = WE.wino_v64(x).view(4, 4, B, H // 2, W // 2, C)
+        U = torch.einsum("xk,ockl,yl->ocxy", G, w, G)
+        y = torch.einsum("ax,by,ocxy,xynhwc->nohawb", AT, AT, U, V).reshape(B, O, H, W)
+        _agree12(y, F.conv2d(x, w, padding=1), "wino_v64")
+        assert (WE.wino_v64(x, absolute=True) >= WE.wino_v64(x).abs() - 1e-12).all()
+        _agree12(F.conv2d(gy, w.flip(2, 3).transpose(0, 1), padding=1), F.conv_transpose2d(gy, w, padding=1), "dgrad as a forward conv")
+        ww = w.clone().requires_grad_(True)
+        (gw,) = torch.autograd.grad(F.conv2d(x, ww, padding=1), ww, gy)
+        _agree12(WE.wgrad64(gy, x), gw, "wgrad64")
