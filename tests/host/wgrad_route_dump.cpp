@@ -2,8 +2,8 @@
 // One line per case:
 //   geometry | mode | u(nscaled) / s(caled) | nsplit -> primary launch [+ twin] ; route fields | tiles per split, splits of the query
 // first over a fixed grid with the default knobs, then once per non-default knob value over a smaller grid, where only the cases are
-// printed whose line differs from the default one (and how many of how many did).  With arguments: the lines of the plane GEMMs asked
-// for (see main).  tests/test_wgrad_route.py builds this with
+// printed whose line differs from the default one (and how many of how many did).  With arguments: the lines of the plane GEMMs and
+// convolutions asked for (see main).  tests/test_wgrad_route.py builds this with
 // AddressSanitizer and UBSan (host code only), runs it and compares the output with tests/golden/wgrad_route_table.txt line by line.
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,6 +58,7 @@ std::string line(const WgradShape& g, int mode, int nsplit, const WgradKnobs& k)
     const WgradRoute r = f16 ? wgrad_route_f16(g, nsplit, k) : wgrad_route(g, mode, nsplit, k);
     char head[200], tail[200];
     if (g.planes) snprintf(head, sizeof head, "planes tiles%d Cs%d Cb%d", g.Ws, g.Cs, g.Cb);
+    else if (g.KH != g.KW) snprintf(head, sizeof head, "B%d Hs%d Ws%d Cs%d Cb%d k%dx%d s%d p%d", g.B, g.Hs, g.Ws, g.Cs, g.Cb, g.KH, g.KW, g.stride, g.pad);
     else snprintf(head, sizeof head, "B%d Hs%d Ws%d Cs%d Cb%d k%d s%d p%d", g.B, g.Hs, g.Ws, g.Cs, g.Cb, g.KH, g.stride, g.pad);
     snprintf(tail, sizeof tail, " ; RP%d CP%d t%d tq%d tpq%d stab%d chunk%ld fam%d | tiles %ld splits %d", r.RP, r.CP, r.tile_f16, r.tiles_q, r.tiles_pq,
              r.stab_nb, r.chunk, r.family, tiles, splits);
@@ -149,17 +150,31 @@ std::vector<Case> knob_grid() {
 
 }  // namespace
 
-// `planes <ntiles> <CsP> <CbP> <mode> <nsplit>` (any number of such groups): one line per group for the plane GEMMs of that Winograd
-// weight gradient instead of the table (tests/test_cpu_wiring.py asks for the rows of tests/test_gpu_winograd_edges.py this way)
+// Argument groups, any number of them, one line per group instead of the table:
+//   planes <ntiles> <CsP> <CbP> <mode> <nsplit>: the plane GEMMs of that Winograd weight gradient (tests/test_cpu_wiring.py asks for the
+//     rows of tests/test_gpu_winograd_edges.py this way)
+//   conv <B> <Hs> <Ws> <Cs> <Cb> <KH> <KW> <stride> <pad> <scaled> <mode> <nsplit>: a direct weight gradient by the shape of its small
+//     side (mode 3: f16 operands; nsplit 0: the query's count) — the rows of tests/test_gpu_wgrad_edges.py
 int main(int argc, char** argv) {
     const WgradKnobs def;
     if (argc > 1) {
-        if ((argc - 1) % 6 != 0) return 2;
-        for (int i = 1; i < argc; i += 6) {
-            if (strcmp(argv[i], "planes") != 0) return 2;
-            const int mode = atoi(argv[i + 4]);
-            if (mode < 0 || mode > 2) return 2;
-            puts(line(planes(atol(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3])), mode, atoi(argv[i + 5]), def).c_str());
+        for (int i = 1; i < argc;) {
+            if (strcmp(argv[i], "planes") == 0 && i + 6 <= argc) {
+                const int mode = atoi(argv[i + 4]);
+                if (mode < 0 || mode > 2) return 2;
+                puts(line(planes(atol(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3])), mode, atoi(argv[i + 5]), def).c_str());
+                i += 6;
+            } else if (strcmp(argv[i], "conv") == 0 && i + 13 <= argc) {
+                int a[12];
+                for (int j = 0; j < 12; ++j) a[j] = atoi(argv[i + 1 + j]);
+                const int KH = a[5], KW = a[6], stride = a[7], pad = a[8], mode = a[10];
+                const int Hb = (a[1] - 1) * stride + KH - 2 * pad, Wb = (a[2] - 1) * stride + KW - 2 * pad;
+                if (mode < 0 || mode > kMode16 || a[0] < 1 || Hb < 1 || Wb < 1 || a[3] < 1 || a[4] < 1 || KH < 1 || KW < 1 || stride < 1) return 2;
+                puts(line(WgradShape{a[0], Hb, Wb, a[4], a[1], a[2], a[3], KH, KW, stride, pad, a[9] != 0, false}, mode, a[11], def).c_str());
+                i += 13;
+            } else {
+                return 2;
+            }
         }
         return 0;
     }

@@ -808,3 +808,114 @@ def test_winograd_edges_restatements():
         ww = w.clone().requires_grad_(True)
         (gw,) = torch.autograd.grad(F.conv2d(x, ww, padding=1), ww, gy)
         _agree12(WE.wgrad64(gy, x), gw, "wgrad64")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tests/test_gpu_wgrad_edges.py: what each row claims about its launch (kernel, tile, stage depth, scale table, grouped taps, twin,
+# chunk, table rows, empty splits, family), held against csrc/wgrad_route.h through tests/host/wgrad_route_dump.cpp (a stand-alone
+# host program under AddressSanitizer and UBSan), and its fp64 reference tied to ATen float64.  No GPU.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _wgrad_edges():
+    import test_gpu_wgrad_edges as GE
+    return GE
+
+
+def test_wgrad_edges_rows_sit_on_their_edges(tmp_path):
+    import re
+    import subprocess
+    GE = _wgrad_edges()
+    exe = str(tmp_path / "wgrad_route_dump")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    flags = "-x c++ -std=c++17 -O1 -g -Wall -Werror -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
+    built = subprocess.run([hipcc] + flags.split() + ["-I", os.path.join(ROOT, "gif_amd", "csrc"),
+                                                      os.path.join(ROOT, "tests", "host", "wgrad_route_dump.cpp"), "-o", exe],
+                           capture_output=True, text=True, timeout=600)
+    assert built.returncode == 0, built.stderr[-4000:]
+    names = [r.name for r in GE.ROWS]
+    assert len(set(names)) == len(names)
+    cases = [(r, m) for r in GE.ROWS for m in r.modes]
+    assert set(GE.CLAIMS) == {(r.name, m) for r, m in cases}, "CLAIMS must cover every (row, mode) and nothing else"
+    args = [a for r, m in cases for a in GE.dump_args(r, m)]
+    ran = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300)
+    assert ran.returncode == 0, (ran.returncode, ran.stderr[-4000:])
+    lines = ran.stdout.splitlines()
+    assert len(lines) == len(cases)
+    for (r, m), l in zip(cases, lines):
+        B, Hs, Ws, Cs, Cb, KH, KW, s, p = GE.geom_of(r, m)
+        assert Cs % (8 if m == "f16" else 4) == 0 and Cb % (8 if m == "f16" else 4) == 0 and 1 <= KH <= 3 and 1 <= KW <= 3 and s in (1, 2), r.name
+        assert min(GE.big_hw(GE.geom_of(r, m))) >= 1, r.name
+        assert GE.claim_of_line(l, r, m) == GE.CLAIMS[r.name, m], (r.name, m, l)
+    C = GE.CLAIMS
+    by = {r.name: r for r in GE.ROWS}
+    # ---- the facts the row comments name
+    for route in ("thin", "sq", "tiny"):
+        for m in GE.ALL:
+            assert C[f"ch_{route}_n16", m][1:4] == (32, 1, 0) and C[f"ch_{route}_n33_1", m][1] == 64 and C[f"ch_{route}_n33_2", m][1] == 32
+            assert C[f"ch_{route}_n130_5", m][1:4:2] == (32, 0) and C[f"ch_{route}_n130_6", m][1:4:2] == (32, 1) and C[f"ch_{route}_b3_n2", m][1] == 64
+    for m in GE.FP32_MODES:
+        assert C["sm_256x257", m] == ("small", 320, 0, 50, 1) and C["sm_1x65537", m] == ("small", 320, 0, 51, 1)
+        assert C["sm_not_255x257", m][0].startswith("mfma f32 32x32 ") and C["tb_65", m][0] == "mfma f32 128x128 w2x2 glds0 bkp32 tab0 x3=0"
+        assert C["tb_65", m][2] == 65 and C["tb_45", m][2] == 45 and " tab1 " in C["tb_45", m][0]
+    assert 65537 - 204 * 320 == 257 and 205 * 320 >= 65537  # sm_1x65537: the last non-empty split
+    assert C["sm_not_255x257", "native"][1:4:2] == (608, 5) and C["hl_511", "f16"][1:4:2] == (576, 2)  # empty splits with the library's own count
+    assert C["tb_f16_17", "f16"][:3] == ("mfma f16 128x128 w2x2 glds1 bkp32 tab1 x3=0", 4096, 17)
+    assert C["tb_f16_9", "f16"][:3] == ("mfma f16 256x256 w2x4 glds1 bkp32 tab1 x3=0", 2048, 9)
+    assert C["tb_b4_n3", "native"][1:3] == (64, 3) and C["tb_b_past", "native"][1:3] == (64, 3)
+    taps = {"tp_cb4": (9, 1), "tp_cb12": (9, 1), "tp_cb16": (8, 2), "tp_cb20": (6, 2), "tp_cb24": (5, 2), "tp_cb28": (4, 3), "tp_cb32": (4, 3),
+            "tp_cb24_2x2": (4, 1), "tp_cb24_1x3": (3, 1), "tp_cb24_rows2": (5, 2)}
+    for n, (tpt, tg) in taps.items():
+        assert C[n, "f16x2"][0].startswith(f"h2v2 tab0 taps tpt{tpt} tg{tg} + mfma f32 128x32 w2x1 "), n
+        T, Cb = by[n].geom[5] * by[n].geom[6], by[n].geom[4]
+        assert tpt == min(128 // Cb, T) and tg == -(-T // tpt)
+    assert {T - (tg - 1) * tpt for T, (tpt, tg) in ((9, taps[n]) for n in ("tp_cb16", "tp_cb28", "tp_cb32"))} == {1}  # a last group of ONE tap
+    assert C["tp_cb24_1x1", "f16x2"][0].startswith("mfma f32 128x32 w2x1 glds1 bkp32 tab0 x3=2 + ")
+    assert {C[n, "f16"][0] for n in by if n.startswith("hl_") and n != "hl_511"} == {"halo tr1"} and C["hl_511", "f16"][0].startswith("mfma f16 32x32 ")
+    patches = {n: by[n].geom[0] * -(-by[n].geom[1] // 16) * -(-by[n].geom[2] // 16) for n in by if n.startswith("hl_")}
+    assert (patches["hl_513"], patches["hl_1025"], patches["hl_511"], patches["hl_xsample_sc"]) == (513, 1025, 511, 578)
+    for n in by:
+        if n.startswith("cu16_") or n in ("lad_tab16", "tb_b4_n3", "tb_45"):
+            assert all(" bkp16 " in C[n, m][0] for m in by[n].modes), n
+        if n.startswith("cu_") and n.endswith(("_sc", "_sc_s2")) and n != "cu_b3_1x32_sc":
+            assert " glds0 " in C[n, "native"][0], n
+    gg = GE.GUARD_GEOM
+    assert gg[0] * gg[1] * gg[2] == 160 and -(-160 // GE.GUARD_NSPLIT) <= 32 and (GE.GUARD_NSPLIT - 1) * 32 >= 160  # the last split is empty
+    # ---- section 5 names every launch of the default-knob route table (conv geometries); small and halo have sections of their own
+    def sig(launch):
+        return re.sub(r" tpt\d+ tg\d+", "", launch)
+    ladder = {sig(C[r.name, m][0]) for r in GE.ROWS if r.ladder for m in r.modes}
+    with open(os.path.join(ROOT, "tests", "golden", "wgrad_route_table.txt")) as f:
+        table = set()
+        for l in f.read().splitlines():
+            if l.startswith(("GIF_", "planes")):
+                continue
+            launch = re.search(r" -> (.*?) ; RP", l).group(1)
+            table.add(sig(re.sub(r" thr\d+ wgs\d+", "", launch).replace(" + twin ", " + ")))
+    assert {"small", "halo tr1"} <= table and {"small", "halo tr1"} <= {c[0] for c in C.values()}
+    assert table - {"small", "halo tr1"} <= ladder, sorted(table - ladder)
+    assert len(ladder) >= 25, sorted(ladder)
+
+
+def test_wgrad_edges_reference_is_the_weight_gradient():
+    """wgrad64 against autograd of F.conv2d in ATen float64: non-square kernels, stride 2, padding, per-sample scales, wscale."""
+    GE = _wgrad_edges()
+    g = torch.Generator().manual_seed(12)
+    for B, Hs, Ws, Cs, Cb, KH, KW, s, p in ((2, 5, 7, 3, 4, 3, 3, 1, 1), (2, 5, 7, 3, 4, 3, 3, 2, 0), (3, 4, 6, 2, 5, 1, 3, 1, 0),
+                                            (1, 5, 6, 4, 3, 3, 1, 1, 1), (2, 4, 4, 3, 3, 2, 2, 1, 1), (2, 3, 5, 2, 2, 2, 3, 1, 0),
+                                            (2, 1, 9, 3, 2, 3, 3, 1, 1), (1, 6, 5, 2, 3, 1, 1, 1, 0), (2, 3, 4, 3, 2, 2, 3, 2, 0)):
+        Hb, Wb = GE.big_hw((B, Hs, Ws, Cs, Cb, KH, KW, s, p))
+        x = torch.randn(B, Cb, Hb, Wb, generator=g, dtype=torch.float64)
+        gy = torch.randn(B, Cs, Hs, Ws, generator=g, dtype=torch.float64)
+        ss, bs = torch.rand(B, Cs, generator=g, dtype=torch.float64) + 0.5, torch.rand(B, Cb, generator=g, dtype=torch.float64) + 0.5
+        for sa, sb, wscale in ((None, None, 1.0), (ss, bs, -0.37), (ss, None, 1.0)):
+            w = torch.zeros(Cs, Cb, KH, KW, dtype=torch.float64, requires_grad=True)
+            xs = x if sb is None else x * sb[:, :, None, None]
+            gs = gy if sa is None else gy * sa[:, :, None, None]
+            y = F.conv2d(xs, w, stride=s, padding=p)
+            assert y.shape[2:] == (Hs, Ws)
+            (gw,) = torch.autograd.grad(y, w, gs)
+            _agree12(GE.wgrad64(gy, x, KH, KW, s, p, sa, sb, wscale), wscale * gw, "wgrad64")
+            R = GE.wgrad64(gy, x, KH, KW, s, p, sa, sb, wscale, absolute=True)
+            assert (R >= GE.wgrad64(gy, x, KH, KW, s, p, sa, sb, wscale).abs() - 1e-12).all()
+    # a one-row map: the ky != 1 taps of a padded 3x3 only ever read padding
+    R = GE.wgrad64(torch.ones(1, 2, 1, 9), torch.ones(1, 2, 1, 9), 3, 3, 1, 1, absolute=True)
+    assert (R[:, :, 0] == 0).all() and (R[:, :, 2] == 0).all() and (R[:, :, 1] > 0).all()
