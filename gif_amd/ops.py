@@ -761,7 +761,8 @@ def _raster_workspace(lib, dev, B, F, h, w):
     if ws is None:
         if len(_raster_ws) >= _RASTER_WS_MAX:
             _raster_ws_drop(lib, next(iter(_raster_ws)))
-        ws = torch.zeros((max(lib.gif_rasterize_workspace_bytes(B, F, h, w) // 8, 1),), device=dev, dtype=torch.int64)
+        # (the byte count is a multiple of 4, not of 8: B * tiles * F odd leaves half a word, which must not be cut off)
+        ws = torch.zeros((max((lib.gif_rasterize_workspace_bytes(B, F, h, w) + 7) // 8, 1),), device=dev, dtype=torch.int64)
         _raster_ws[key] = ws
         _lib.check(lib.gif_rasterize_assume_clean_workspace(ws.data_ptr(), 1), "rasterize_assume_clean_workspace")
     return key, ws

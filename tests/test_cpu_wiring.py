@@ -919,3 +919,275 @@ def test_wgrad_edges_reference_is_the_weight_gradient():
     # a one-row map: the ky != 1 taps of a padded 3x3 only ever read padding
     R = GE.wgrad64(torch.ones(1, 2, 1, 9), torch.ones(1, 2, 1, 9), 3, 3, 1, 1, absolute=True)
     assert (R[:, :, 0] == 0).all() and (R[:, :, 2] == 0).all() and (R[:, :, 1] > 0).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tests/test_gpu_raster_edges.py: the edge each row claims, recomputed from the constants of csrc/rasterize.hip by a numpy restatement
+# of front_facing / face_bbox / the tile and band arithmetic, the C oracle's behaviour the rows rely on, and the backward's fp64
+# restatement tied to central differences.  No GPU.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _raster_edges():
+    import test_gpu_raster_edges as RE
+    return RE
+
+
+def test_raster_edges_constants_are_the_sources():
+    """A constant changed in rasterize.hip fails here; it does not silently move a row off its edge."""
+    import re
+    RE = _raster_edges()
+    with open(os.path.join(ROOT, "gif_amd", "csrc", "rasterize.hip")) as f:
+        src = f.read()
+
+    def one(pattern):
+        m = re.findall(pattern, src)
+        assert len(m) == 1, (pattern, m)
+        return m[0]
+
+    got = {name: int(one(r"constexpr int %s = (\d+);" % name))
+           for name in ("kTile", "kSmallArea", "kBinThreads", "kMaxLdsTiles", "kTileThreads", "kBwdWaves")}
+    # the band height of the backward is the tile edge
+    one(r"b0 = y_min / kTile; b1 = y_max / kTile;")
+    one(r"const int r0 = max\(y_min, band \* kTile\), r1 = min\(y_max, band \* kTile \+ kTile - 1\);")
+    one(r"int bwd_bands_per_image\(int H\) \{ return \(H \+ kTile - 1\) / kTile; \}")
+    got["kBand"] = got["kTile"]
+    assert got == RE.K
+    # the expressions geometry() and bands() restate, and the predicates the rows name
+    assert got["kTile"] == 1 << 6
+    one(r"tx0 = x_min >> 6; tx1 = x_max >> 6; ty0 = y_min >> 6; ty1 = y_max >> 6;")
+    one(r"const bool lds = nt <= kMaxLdsTiles;")
+    one(r"if \(area > 0 && area <= kSmallArea\)")
+    one(r"__ballot\(area > kSmallArea\)")
+    one(r"for \(int j0 = 0; j0 < n; j0 \+= kThreads\)")
+    one(r"const uint32_t pre_idx = j_first < F \? min\(cand\[j_first\], \(uint32_t\)\(F - 1\)\) : 0u;")
+    assert len(re.findall(r"raster_tiles<T, (?:true|false), kTileThreads><<<grid, kTileThreads, 0, s>>>", src)) == 2
+    one(r"raster_bin<T><<<dim3\(\(unsigned\)gif::cdiv\(F, kBinThreads\), \(unsigned\)B\), kBinThreads, 0, s>>>")
+    one(r"const int fi = blockIdx\.x \* kBwdWaves \+ \(threadIdx\.x >> 6\), band = blockIdx\.y, b = blockIdx\.z;")
+    one(r"inline long pad2\(long n\) \{ return \(n \+ 1\) / 2 \* 2; \}")
+    one(r"for \(int p = lane; p < n; p \+= 64\)")
+
+
+def _raster_rows(RE):
+    return list(RE.FROWS) + list(RE.WS_ROWS)
+
+
+def test_raster_edges_forward_rows_sit_on_their_edges():
+    RE = _raster_edges()
+    rows = _raster_rows(RE)
+    assert len({r.name for r in rows}) == len(rows)
+    seen = set()
+    for row in rows:
+        fv64, fv32 = RE.face_array(row.faces, np.float64), RE.face_array(row.faces, np.float32)
+        B, F = fv64.shape[:2]
+        assert fv64.shape == (B, F, 3, 3), row.name
+        # the input constraints: exact in fp32, |x|, |y| < 2^31 and finite, no face with z of mixed sign or zero (a NaN z aside), no
+        # caller depth of -0.0
+        assert np.array_equal(fv32.astype(np.float64), fv64, equal_nan=True), row.name
+        assert np.isfinite(fv64[..., :2]).all() and (np.abs(fv64[..., :2]) < 2.0 ** 31).all(), row.name
+        z = fv64[..., 2]
+        zs = np.where(np.isnan(z), np.nanmax(z, -1, keepdims=True), z)
+        assert ((zs > 0).all(-1) | (zs < 0).all(-1)).all(), row.name
+        for fv in (fv32, fv64):
+            depth = RE.caller_buffers(row, fv)[0]
+            assert depth.dtype == fv.dtype and not (np.signbit(depth) & (depth == 0)).any() and not np.isnan(depth).any(), row.name
+        g32, g64 = RE.geometry(fv32, row.H, row.W), RE.geometry(fv64, row.H, row.W)
+        assert np.array_equal(g32["lists"], g64["lists"]) and np.array_equal(g32["box"], g64["box"]), row.name
+        g = g32
+        assert g["lists"].max() <= F and B <= 65535 and row.H * row.W <= 270000, row.name
+        claim = row.claim or {}
+        assert claim, row.name
+        for key, want in claim.items():
+            seen.add(key)
+            if key == "F":
+                assert F == want, (row.name, F)
+            elif key == "groups":
+                assert -(-F // RE.K["kBinThreads"]) == want, (row.name, F)
+            elif key == "nt":
+                assert g["nt"] == want, (row.name, g["nt"])
+            elif key == "lists":
+                for (b, t), n in want.items():
+                    assert g["lists"][b, t] == n, (row.name, b, t, int(g["lists"][b, t]), n)
+            elif key == "areas":
+                for (f, t), a in want.items():
+                    assert g["area"](0, f, t) == a, (row.name, f, t, g["area"](0, f, t), a)
+            else:
+                assert key in ("cover", "tri", "seed", "split", "only_face", "tie_winner", "tie_losers", "shared"), (row.name, key)
+    assert seen >= {"F", "groups", "nt", "lists", "areas", "cover", "tri"}
+    by = {r.name: r for r in rows}
+    geo = lambda n: RE.geometry(RE.face_array(by[n].faces, np.float32), by[n].H, by[n].W)  # noqa: E731
+    # both sides of every predicate of the table
+    assert geo("nt1024")["nt"] == RE.K["kMaxLdsTiles"] and geo("nt1025")["nt"] == RE.K["kMaxLdsTiles"] + 1
+    assert [int(geo(f"list_{n}")["lists"][0, 0]) for n in (511, 512, 513, 1025)] == [511, 512, 513, 1025]
+    assert 2 * RE.K["kTileThreads"] < 1025 and RE.K["kTileThreads"] == 512
+    assert [geo(n)["area"](0, 0, 0) for n in ("cls_4x4", "cls_2x8", "cls_1x16", "cls_16x1")] == [RE.K["kSmallArea"]] * 4
+    assert [geo(n)["area"](0, 0, 0) for n in ("cls_1x17", "cls_2x9")] == [RE.K["kSmallArea"] + 1, RE.K["kSmallArea"] + 2]
+    g = geo("list_513_wave")
+    assert all(g["area"](0, f, 0) > RE.K["kSmallArea"] for f in range(513))  # every ballot bit of round 0, bit 63 included
+    g = geo("list_513")
+    assert all(0 < g["area"](0, f, 0) <= RE.K["kSmallArea"] for f in range(513))
+    assert [by[n].faces[0].__len__() for n in ("bin_f1", "bin_f255", "bin_f256", "bin_f257")] == [1, 255, 256, 257]
+    assert geo("ws_x")["lists"].tolist() != geo("ws_y")["lists"].tolist()
+    assert RE.face_array(RE.WS_X.faces).shape == RE.face_array(RE.WS_Y.faces).shape and (RE.WS_X.H, RE.WS_X.W) == (RE.WS_Y.H, RE.WS_Y.W)
+
+
+def test_raster_edges_the_oracle_behaves_as_the_rows_assume():
+    RE = _raster_edges()
+    by = {r.name: r for r in RE.FROWS}
+
+    def run(name, variant="f32"):
+        fv, fc, bufs, (d, t, p) = RE.forward_case(name, variant)
+        return fv, bufs, d, t, p
+
+    for row in RE.FROWS:
+        claim = row.claim
+        for variant in RE.VARIANTS:
+            fv, bufs, d, t, p = run(row.name, variant)
+            covered = t >= 0
+            assert ((t == -7) | covered).all() and t.max() < fv.shape[1], row.name
+            # an untouched pixel keeps all three caller values
+            assert np.array_equal(d[~covered], bufs[0][~covered]) and np.array_equal(p[~covered], bufs[2][~covered]), row.name
+            assert not np.isnan(d).any() and not np.isnan(p).any(), row.name
+            want = claim.get("cover")
+            if isinstance(want, dict):
+                want = want[variant[1:] == "64" and "f64" or "f32"]
+            if want is not None:
+                assert int(covered.sum()) == want, (row.name, variant, int(covered.sum()))
+            if want != 0:
+                assert covered.any(), (row.name, variant)  # every row that claims coverage has some
+            for (b, y, x), f in claim.get("tri", {}).items():
+                assert t[b, y, x] == f, (row.name, variant, (b, y, x), int(t[b, y, x]))
+            if "only_face" in claim:
+                assert set(np.unique(t[covered])) == {claim["only_face"]}
+            if "tie_winner" in claim:
+                a, b_, c_ = sorted((claim["tie_winner"],) + claim["tie_losers"])
+                assert np.array_equal(fv[0, a], fv[0, b_]) and np.array_equal(fv[0, a], fv[0, c_])
+                own = t[0] == claim["tie_winner"]
+                assert own.sum() == 136 and not np.isin(t, claim["tie_losers"]).any()  # rt(3, 3, 16): the lowest index wins every pixel
+    # the tail face of the bin rows: without it (5, 5) belongs to another face or to nobody
+    for name in ("bin_f255", "bin_f256", "bin_f257"):
+        _, _, _, t, _ = run(name)
+        assert (t == 0).sum() > 100 and len(np.unique(t)) == len(by[name].faces[0]) + 1  # every face wins a pixel (and -7 is left)
+    # list rows: every tiny face wins a pixel, so a face dropped from a round changes the image
+    for name, F in (("list_511", 514), ("list_512", 515), ("list_513", 516), ("list_1025", 1028), ("list_513_wave", 513), ("list_600", 602)):
+        _, _, _, t, _ = run(name)
+        assert len(np.unique(t[t >= 0])) == F, name
+    # coplanar tie: the shared pixels (the hypotenuse x + y = 48) go to face 0 whichever face comes first
+    for variant in ("f32", "f64"):
+        fv, bufs, d, t, p = run("tie_coplanar", variant)
+        swapped = RE.oracle_run(by["tie_coplanar"], np.ascontiguousarray(fv[:, ::-1]), None, bufs)[1]
+        shared = (t[0] == 0) & (swapped[0] == 0)
+        ys, xs = np.nonzero(shared)
+        assert shared.sum() == by["tie_coplanar"].claim["shared"] and (xs + ys == 48).all(), (variant, int(shared.sum()))
+        assert (d[0][t[0] >= 0] == 2).all()
+    # seeded depth, positive z
+    for variant in RE.VARIANTS:
+        fv, bufs, d, t, p = run("seed_pos", variant)
+        first_t, zp = RE._first_pass(by["seed_pos"], fv)
+        x = np.arange(64)[None, None, :]
+        y = np.arange(64)[None, :, None]
+        cov = first_t >= 0
+        caller, tie = cov & (x < RE.SEED_SPLIT_X), cov & (x >= RE.SEED_SPLIT_X) & (y == RE.SEED_TIE_Y)
+        assert caller.sum() >= 10 and tie.sum() >= 4 and (cov & ~caller & ~tie).sum() >= 10
+        assert (t[caller] == -7).all() and (d[caller] == 0.25).all() and np.array_equal(p[caller], bufs[2][caller])  # the caller wins
+        assert (t[tie] == 0).all() and np.array_equal(d[tie], zp[tie]) and np.array_equal(bufs[0][tie], zp[tie])  # the face wins the tie
+        assert (t[cov & ~caller] == 0).all() and np.isinf(d[~cov]).all()
+    # negative z: the two faces split the 36 pixels; against negative caller depths only the pixels nearer than the caller change
+    for variant in ("f32", "f64"):
+        _, _, d, t, _ = run("neg_z", variant)
+        assert sorted(((t == 0).sum(), (t == 1).sum())) == [10, 26] and (d[t >= 0] < 0).all()
+        _, bufs, d2, t2, _ = run("seed_neg", variant)
+        won = t2 >= 0
+        assert 0 < won.sum() < 36 and (d2[won] <= bufs[0][won]).all() and np.array_equal(d2[won], d[won]) and np.array_equal(t2[won], t[won])
+        lost = (t >= 0) & ~won
+        assert (d[lost] > bufs[0][lost]).all() and (bufs[0][lost] == -2.25).all() and (bufs[0][won] == -2.25).any() and (bufs[0][won] == -1).any()
+    # the rounding-degenerate face: its fp32 den is exactly 0 and it writes -0.0 barycentrics
+    _, _, _, t, p = run("degen_round", "f32")
+    assert (t[0, :2] == 0).all() and (t[0, 2:] == -7).all()
+    assert (p[0, :2, :, 0] == 1).all() and (p[0, :2, :, 1:] == 0).all() and np.signbit(p[0, :2, :, 1:]).any()
+    _, _, _, t, _ = run("degen_round", "f64")
+    assert (t[0, 0] == 0).all() and (t[0, 1:] == -7).all()
+
+
+def test_raster_edges_backward_rows_sit_on_their_edges():
+    RE = _raster_edges()
+    assert len({r.name for r in RE.BROWS}) == len(RE.BROWS)
+    seen = set()
+    for row in RE.BROWS:
+        c = RE.backward_case(row.name)
+        fv = c["fv"].numpy()
+        B, F = fv.shape[:2]
+        assert 16 <= row.W <= 64 or row.name in RE.B_DEGENERATE
+        b0, b1, n = RE.bands(fv, row.H, row.W)
+        npix = c["ref"]["npix"]
+        for key, want in row.claim.items():
+            seen.add(key)
+            for k, v in want.items():
+                if key == "bands":
+                    assert (b0[0, k], b1[0, k]) == v, (row.name, k, (int(b0[0, k]), int(b1[0, k])))
+                elif key == "n":
+                    assert n(0, k[0], k[1]) == v, (row.name, k, n(0, *k))
+                else:
+                    assert key == "wins" and bool(npix[0, k] > 0) == v, (row.name, k, int(npix[0, k]))
+        assert b1.max() < -(-row.H // RE.K["kBand"])
+        # a face owns pixels only inside its own bands
+        for b, f in zip(*np.nonzero(npix.numpy() > 0)):
+            ys = np.nonzero((c["tri"][b].numpy() == f).any(1))[0]
+            assert b0[b, f] <= ys.min() // 64 and ys.max() // 64 <= b1[b, f], (row.name, b, f)
+        # the accuracy condition: every face that wins a pixel is well shaped
+        if row.name in RE.B_DEGENERATE:
+            p = fv[0, 0, :, :2]  # its fp32 den is exactly zero
+            v0, v1 = p[2] - p[0], p[1] - p[0]
+            d00, d01, d11 = v0 @ v0, v0 @ v1, v1 @ v1
+            assert np.float32(d00 * d11) - np.float32(d01 * d01) == 0 and d00.dtype == np.float32
+            continue
+        p = fv[..., :2].astype(np.float64)
+        v0, v1, v2 = p[:, :, 2] - p[:, :, 0], p[:, :, 1] - p[:, :, 0], p[:, :, 2] - p[:, :, 1]
+        d00, d01, d11 = (v0 * v0).sum(-1), (v0 * v1).sum(-1), (v1 * v1).sum(-1)
+        den = d00 * d11 - d01 * d01  # (twice the area) squared
+        longest = np.sqrt(np.maximum(np.maximum(d00, d11), (v2 * v2).sum(-1)))
+        win = npix.numpy() > 0
+        assert (den[win] / (d00 * d11)[win] >= 0.25).all(), row.name
+        assert (np.sqrt(den[win]) / longest[win] >= 2).all(), row.name  # the smallest altitude
+        assert (npix.numpy()[win] >= 10).all(), row.name
+    assert seen == {"bands", "n", "wins"}
+    ns = RE.BROW["bw_n"].claim["n"]
+    assert sorted(ns.values()) == [63, 64, 65, 200]
+    assert [len(RE.BROW[f"bw_f{k}"].faces[0]) for k in (1, 4, 5, 7)] == [1, 4, 5, 7] and RE.K["kBwdWaves"] == 4
+    assert [-(-RE.BROW[n].H // 64) for n in ("bw_h64", "bw_h65", "bw_h192")] == [1, 2, 3]
+
+
+@pytest.mark.parametrize("name", ["bw_f4", "bw_hidden"])
+def test_raster_edges_backward_restatement_is_the_derivative(name):
+    """The autograd gradient of bwd_ref equals a central difference of the interpolated image in fp64, tri held fixed."""
+    RE = _raster_edges()
+    c = RE.backward_case(name)
+    fv, fc, tri, g = c["fv"].double(), c["fc"].double(), c["tri"], c["g"].double()
+    B, F = fv.shape[:2]
+    bi, yi, xi = torch.nonzero(tri >= 0, as_tuple=True)
+    fo = bi * F + tri[bi, yi, xi].long()
+
+    def loss(v, a):
+        w, _ = RE.bary64(v.reshape(B * F, 3, 3)[fo][:, :, :2], torch.stack([xi, yi], -1).double())
+        return ((w[..., None] * a.reshape(B * F, 3, 3)[fo]).sum(1) * g[bi, yi, xi]).sum()
+
+    gen = torch.Generator().manual_seed(3)
+    delta = 1e-6
+    for k in range(4):
+        dv = torch.randn(fv.shape, generator=gen, dtype=torch.float64)
+        da = torch.randn(fc.shape, generator=gen, dtype=torch.float64)
+        fd = (loss(fv + delta * dv, fc + delta * da) - loss(fv - delta * dv, fc - delta * da)) / (2 * delta)
+        an = (c["ref"]["gfv"] * dv).sum() + (c["ref"]["gfc"] * da).sum()
+        assert abs(fd.item() - an.item()) <= 1e-6 * max(abs(an.item()), 1.0), (k, fd.item(), an.item())
+    assert (c["ref"]["gfv"][..., 2] == 0).all() and (c["ref"]["Rv"] >= c["ref"]["gfv"].abs() - 1e-12).all()
+    assert (c["ref"]["Rc"] >= c["ref"]["gfc"].abs() - 1e-12).all()
+
+
+def test_raster_edges_gather_reference_is_the_gradient_of_face_vertices():
+    RE = _raster_edges()
+    for name, B, V in RE.GROWS:
+        faces = RE.gather_faces(name, V)
+        assert int(faces.max()) < V - 1 and B * V in (255, 256, 257, 258, 16)
+        gface = torch.randint(-8, 9, (B, faces.shape[0], 3, 3), generator=torch.Generator().manual_seed(1)).double()
+        x = torch.zeros(B, V, 3, dtype=torch.float64, requires_grad=True)
+        (gx,) = torch.autograd.grad(x[:, faces], x, gface)
+        assert torch.equal(gx, RE.gather_ref(gface, faces, V).double())
+        assert gface.abs().max() * faces.shape[0] * 3 < 2 ** 24  # every fp32 sum is exact
