@@ -194,16 +194,14 @@ def _cached_weight_op(w, tag, build):
 
 X3_TAPDENSE = _lib.knob("GIF_X3_TAPDENSE", "1") != "0"  # tap-dense K order for 3x3 layers with 8..28 contraction channels (A/B)
 X3_MIN_CIN = int(_lib.knob("GIF_X3_MIN_CIN", "24"))  # gif_conv2d_x3_eligible: >= 24 (one zero-padded 32-float K chunk)
-
-
-X3_MAX_INPUT_BYTES = (1 << 32) - (1 << 26)  # the bf16x3 / f16 kernels address their input through 32-bit buffer offsets (conv_igemm.hip)
+# The bf16x3 / f16 kernels address their input through 32-bit buffer offsets (conv_igemm.hip): launches the buffer-addressed DMA does
+# not take (>= 4 GiB of input) stay on the native fp32 kernel.  conv_plan applies the rule.
+X3_MAX_INPUT_BYTES = (1 << 32) - (1 << 26)
 
 
 def x3_conv(dtype, cin_act: int, src=None, spec=None) -> bool:
-    """fp32 conv fwd/dgrad with `cin_act` contraction channels runs on the bf16x3 kernels (mode + eligibility).  Launches the
-    buffer-addressed DMA does not take (>= 4 GiB of input) stay on the native fp32 kernel."""
-    if src is not None and src.numel() * src.element_size() > X3_MAX_INPUT_BYTES:
-        return False
+    """fp32 conv fwd/dgrad with `cin_act` contraction channels runs on the bf16x3 kernels (mode + eligibility; src and spec are not
+    looked at: the size of the input is conv_plan's question)."""
     return dtype == torch.float32 and cin_act >= X3_MIN_CIN and split_mode()
 
 
@@ -214,8 +212,6 @@ def split_mode() -> bool:
 
 H2_CONV = _lib.knob("GIF_H2_CONV", "1") != "0"    # f16x2 mode: direct fwd / dgrad kernels (A/B knobs per kernel family)
 H2_WGRAD = _lib.knob("GIF_H2_WGRAD", "1") != "0"  # f16x2 mode: weight-gradient kernels (direct and Winograd plane GEMMs)
-
-
 H2_WINO = _lib.knob("GIF_H2_WINO", "1") != "0"    # f16x2 mode: Winograd fwd / dgrad GEMM
 H2_GUARD = True  # False: f16x2 launches run without their guarded bf16x3 twin (tests only: shows what the guard protects against)
 
@@ -244,73 +240,64 @@ def x3_tapdense(dtype, cin_act: int, spec, transposed: bool, epi, cout_act: int 
     return cin_act >= 12 and (cout_act > 32 or cin_act < X3_MIN_CIN)
 
 
+def _weight_view(w, rows_are_out: bool, cout_act: int, cin_act: int):
+    """(R, C, sr, sc, sky, skx): rows, columns and element strides of the operand a canonical weight view w[O,I,KH,KW] (any strides) packs
+    into.  rows_are_out=True: rows = O, cols = I (forward); False: rows = I, cols = O (data gradient)."""
+    O, I = w.shape[:2]
+    so, si, sky, skx = w.stride()
+    R, C, sr, sc = (O, I, so, si) if rows_are_out else (I, O, si, so)
+    assert R <= cout_act and C <= cin_act, (R, cout_act, C, cin_act)
+    return R, C, sr, sc, sky, skx
+
+
+def _dims(query, rows: int, cols: int, what: str):
+    """(RP, CP) of one of the library's padded-dimension queries."""
+    RP, CP = ctypes.c_int(), ctypes.c_int()
+    _lib.check(query(rows, cols, ctypes.byref(RP), ctypes.byref(CP)), what)
+    return RP.value, CP.value
+
+
+def _pack(w, rows_are_out, cout_act, cin_act, scale, dtype, form, tapdense):
+    """pack_weight / pack_weight_h2x3: `form` is the family of gif_pack_weight_<form>[_tapdense] ("f32h2x3": both operands of an f16x2 launch)."""
+    lib = _lib.load()
+    KH, KW = w.shape[2:]
+    R, C, sr, sc, sky, skx = _weight_view(w, rows_are_out, cout_act, cin_act)
+
+    def build():
+        RP, CP = _dims(getattr(lib, "gif_conv2d_pack_dims" + {"f32": "", "f16": "_f16"}.get(form, "_x3")), cout_act, cin_act, "pack_dims")
+        T, CPk = (lib.gif_conv2d_x3_tapdense_steps(cin_act, KH, KW), 32) if tapdense else (KH * KW, CP)
+        geo = (R, C, cin_act, KH, KW, RP) if tapdense else (R, C, KH, KW, RP, CP)
+        shapes = []
+        if "h2" in form:  # [row exponents + flag][tap][2][RP][CP] f16, an opaque byte buffer
+            nbytes = lib.gif_pack_weight_f32h2_tapdense_bytes(cin_act, KH, KW, RP) if tapdense else lib.gif_pack_weight_f32h2_bytes(KH, KW, RP, CP)
+            shapes.append(((nbytes,), torch.uint8))
+        if "x3" in form:
+            shapes.append(((T, 3, RP, CPk), torch.bfloat16))
+        wp = [torch.empty(s, device=w.device, dtype=t) for s, t in shapes or [((T, RP, CP), dtype)]]
+        name = "pack_weight_" + form + ("_tapdense" if tapdense else "")
+        _lib.check(getattr(lib, "gif_" + name)(w.data_ptr(), *[p.data_ptr() for p in wp], *geo, sr, sc, sky, skx, float(scale), _stream()), name)
+        return tuple(wp) if form == "f32h2x3" else wp[0]
+
+    return _cached_weight_op(w, ("pack", rows_are_out, cout_act, cin_act, float(scale), dtype, form, bool(tapdense)), build)
+
+
 def pack_weight(w: torch.Tensor, rows_are_out: bool, cout_act: int, cin_act: int, scale: float = 1.0, dtype=torch.float32, x3=False,
                 tapdense=False, h2=False):
     """Pack a canonical forward-conv weight view w[O,I,KH,KW] (any strides) into [T][RP][CP] of `dtype` (fp32 or f16), or
-    (x3=True) into the pre-split bf16x3 operand [T][3][RP][CP] (bf16) of the gif_conv2d_*_f32x3 entry points.
+    (x3=True) into the pre-split bf16x3 operand [T][3][RP][CP] (bf16) of the gif_conv2d_*_f32x3 entry points, (tapdense=True) into that
+    operand in the tap-dense K order [steps][3][RP][32], or (h2=True) into the f16x2 operand.
 
     rows_are_out=True : rows = O, cols = I (operand of gif_conv2d_fwd)
     rows_are_out=False: rows = I, cols = O (operand of gif_conv2d_bwd_data)
     cout_act / cin_act are the channel counts of the op's output / input ACTIVATIONS (>= canonical counts).
     """
-    lib = _lib.load()
-    O, I, KH, KW = w.shape
-    so, si, sky, skx = w.stride()
-    R, C, sr, sc = (O, I, so, si) if rows_are_out else (I, O, si, so)
-    assert R <= cout_act and C <= cin_act, (R, cout_act, C, cin_act)
-    f16 = dtype == torch.float16
-
-    def build():
-        RP, CP = ctypes.c_int(), ctypes.c_int()
-        dims = lib.gif_conv2d_pack_dims_x3 if (x3 or tapdense or h2) else (lib.gif_conv2d_pack_dims_f16 if f16 else lib.gif_conv2d_pack_dims)
-        _lib.check(dims(cout_act, cin_act, ctypes.byref(RP), ctypes.byref(CP)), "pack_dims")
-        if tapdense:
-            steps = lib.gif_conv2d_x3_tapdense_steps(cin_act, KH, KW)
-            wp = torch.empty((steps, 3, RP.value, 32), device=w.device, dtype=torch.bfloat16)
-            _lib.check(lib.gif_pack_weight_f32x3_tapdense(w.data_ptr(), wp.data_ptr(), R, C, cin_act, KH, KW, RP.value, sr, sc, sky, skx,
-                                                          float(scale), _stream()), "pack_weight_tapdense")
-            return wp
-        if h2:  # f16x2 packing: [row exponents + flag][tap][2][RP][CP] f16, an opaque byte buffer
-            wp = torch.empty((lib.gif_pack_weight_f32h2_bytes(KH, KW, RP.value, CP.value),), device=w.device, dtype=torch.uint8)
-            fn = lib.gif_pack_weight_f32h2
-        elif x3:
-            wp = torch.empty((KH * KW, 3, RP.value, CP.value), device=w.device, dtype=torch.bfloat16)
-            fn = lib.gif_pack_weight_f32x3
-        else:
-            wp = torch.empty((KH * KW, RP.value, CP.value), device=w.device, dtype=dtype)
-            fn = _fn("pack_weight", dtype)
-        _lib.check(fn(w.data_ptr(), wp.data_ptr(), R, C, KH, KW, RP.value, CP.value, sr, sc, sky, skx, float(scale), _stream()),
-                   "pack_weight")
-        return wp
-
-    return _cached_weight_op(w, ("pack", rows_are_out, cout_act, cin_act, float(scale), dtype, bool(x3), bool(tapdense), bool(h2)), build)
+    form = "f32x3" if tapdense else "f32h2" if h2 else "f32x3" if x3 else "f16" if dtype == torch.float16 else "f32"
+    return _pack(w, rows_are_out, cout_act, cin_act, scale, dtype, form, tapdense)
 
 
 def pack_weight_h2x3(w: torch.Tensor, rows_are_out: bool, cout_act: int, cin_act: int, scale: float = 1.0, tapdense=False):
     """(wp2, wp3): the f16x2 packing and the bf16x3 packing (the guarded fallback's operand) of the same weight view, ONE launch."""
-    lib = _lib.load()
-    O, I, KH, KW = w.shape
-    so, si, sky, skx = w.stride()
-    R, C, sr, sc = (O, I, so, si) if rows_are_out else (I, O, si, so)
-    assert R <= cout_act and C <= cin_act, (R, cout_act, C, cin_act)
-
-    def build():
-        RP, CP = ctypes.c_int(), ctypes.c_int()
-        _lib.check(lib.gif_conv2d_pack_dims_x3(cout_act, cin_act, ctypes.byref(RP), ctypes.byref(CP)), "pack_dims")
-        if tapdense:
-            steps = lib.gif_conv2d_x3_tapdense_steps(cin_act, KH, KW)
-            wp2 = torch.empty((lib.gif_pack_weight_f32h2_tapdense_bytes(cin_act, KH, KW, RP.value),), device=w.device, dtype=torch.uint8)
-            wp3 = torch.empty((steps, 3, RP.value, 32), device=w.device, dtype=torch.bfloat16)
-            _lib.check(lib.gif_pack_weight_f32h2x3_tapdense(w.data_ptr(), wp2.data_ptr(), wp3.data_ptr(), R, C, cin_act, KH, KW, RP.value, sr, sc,
-                                                            sky, skx, float(scale), _stream()), "pack_weight_f32h2x3_tapdense")
-            return wp2, wp3
-        wp2 = torch.empty((lib.gif_pack_weight_f32h2_bytes(KH, KW, RP.value, CP.value),), device=w.device, dtype=torch.uint8)
-        wp3 = torch.empty((KH * KW, 3, RP.value, CP.value), device=w.device, dtype=torch.bfloat16)
-        _lib.check(lib.gif_pack_weight_f32h2x3(w.data_ptr(), wp2.data_ptr(), wp3.data_ptr(), R, C, KH, KW, RP.value, CP.value, sr, sc, sky, skx,
-                                               float(scale), _stream()), "pack_weight_f32h2x3")
-        return wp2, wp3
-
-    return _cached_weight_op(w, ("pack_h2x3", rows_are_out, cout_act, cin_act, float(scale), bool(tapdense)), build)
+    return _pack(w, rows_are_out, cout_act, cin_act, scale, torch.float32, "f32h2x3", tapdense)
 
 
 # Winograd F(2x2,3x3) dispatch for stride-1 / pad-1 3x3 convs (conv_winograd.hip).  GIF_WINOGRAD=0 forces the direct
@@ -359,6 +346,67 @@ def winograd_eligible(spec: ConvSpec, B, H, W, cin_act, cout_act=64, min_tiles=N
             and min(cin_act, cout_act) >= min_c and B * (H // 2) * (W // 2) >= min_tiles)
 
 
+class ConvPlan(NamedTuple):
+    """What one convolution runs, decided before the library is called (conv_plan)."""
+    route: str   # "winograd" | "direct"
+    mode: str    # "native" | "bf16x3" | "f16x2" | "f16": the entry-point family of the library call (FAMILY)
+    dense: bool  # direct route only: the tap-dense entry point
+
+
+def _fp32_mode(x3, h2) -> str:
+    """Contraction mode of an fp32 launch that has a bf16x3 form (x3) and an f16x2 form (h2: its A/B knob): f16x2, else split, else native."""
+    if not (x3 and split_mode()):
+        return "native"
+    return "f16x2" if h2 and get_fp32_mfma_mode() == "f16x2" else "bf16x3"
+
+
+def winograd_mode(op: str, cout_act: int) -> str:
+    """Contraction mode of the Winograd route's GEMMs (op "wgrad": the plane GEMMs of the weight gradient; else fwd / dgrad).
+    fwd / dgrad: the split GEMM's 128-wide N tile wants full tiles; other channel counts stay on the native GEMM (GIF_WINO_X3=0: A/B)."""
+    if op == "wgrad":
+        return _fp32_mode(True, H2_WGRAD)
+    return _fp32_mode(WINOGRAD_X3 and cout_act % 128 == 0, H2_WINO)
+
+
+def conv_plan(op: str, dtype, B, spec: ConvSpec, big_hw, small_hw, cin_act: int, cout_act: int, epi=None, in_bytes: int = 0) -> ConvPlan:
+    """Route, contraction mode and K order of one convolution: everything conv_fwd, conv_bwd_data and conv_wgrad decide before they call the
+    library.  Pure: reads its arguments, the knobs above and get_fp32_mfma_mode(); tests/golden/conv_plan_table.txt records its answers.
+
+    op: "fwd" | "dgrad" | "wgrad".  big_hw / small_hw: the two sides of the forward convolution, (H, W) tuples.  cin_act / cout_act: contraction and output
+    channel counts of THIS op as the activations carry them (fwd: Cb, Cs; dgrad: Cs, Cb; wgrad: Cb, Cs).  epi: the epilogue arguments
+    (x3_tapdense looks for in_scale).  in_bytes: size of the fwd / dgrad input; past X3_MAX_INPUT_BYTES a direct launch stays native."""
+    wgrad, f16 = op == "wgrad", dtype == torch.float16
+    # the weight gradient has thresholds of its own (None: winograd_eligible's); the two sides of a forward 3x3 / stride 1 / pad 1 are one size
+    min_tiles, min_c = (min(WINOGRAD_MIN_TILES, WINOGRAD_WGRAD_MIN_TILES), _winograd_min_c(WINOGRAD_WGRAD_MIN_C)) if wgrad else (None, None)
+    if (big_hw == small_hw and (not wgrad or (WINOGRAD_WGRAD and cin_act >= 64 and cout_act >= 64))
+            and winograd_eligible(spec, B, *small_hw, cin_act, cout_act, min_tiles, dtype, min_c)):
+        return ConvPlan("winograd", winograd_mode(op, cout_act), False)
+    if wgrad:
+        return ConvPlan("direct", "f16" if f16 else _fp32_mode(True, H2_WGRAD), False)
+    x3 = x3_conv(dtype, cin_act)
+    dense = x3_tapdense(dtype, cin_act, spec, op == "dgrad", {} if epi is None else epi, cout_act)
+    if in_bytes > X3_MAX_INPUT_BYTES:
+        x3 = dense = False
+    return ConvPlan("direct", "f16x2" if h2_conv(x3, dense) else "bf16x3" if (x3 or dense) else "f16" if f16 else "native", bool(dense))
+
+
+# Entry-point family of each contraction mode: gif_<op>_<family>[_tapdense]
+FAMILY = {"native": "f32", "bf16x3": "f32x3", "f16x2": "f32h2", "f16": "f16"}
+
+
+def _call(op: str, mode: str, *args, dense=False):
+    """Call gif_<op>_<family of mode>[_tapdense](*args) and check its status."""
+    name = f"{op}_{FAMILY[mode]}" + ("_tapdense" if dense else "")
+    _lib.check(getattr(_lib.load(), "gif_" + name)(*args), name)
+
+
+def _weight_ptrs(wp):
+    """Pointer arguments of packed weights: one operand, or the f16x2 pair (the guarded bf16x3 twin's operand second: None with H2_GUARD off)."""
+    if isinstance(wp, torch.Tensor):
+        return (wp.data_ptr(),)
+    return (wp[0].data_ptr(), wp[1].data_ptr() if H2_GUARD else None)
+
+
 def conv3x3_winograd(x, w, rows_are_out: bool, cout_act: int, wscale=1.0, keep_v=False, **epi):
     """act(out_scale * conv3x3_s1_p1(in_scale * x, w) + residual + bias) via Winograd F(2x2,3x3).
 
@@ -369,48 +417,23 @@ def conv3x3_winograd(x, w, rows_are_out: bool, cout_act: int, wscale=1.0, keep_v
     lib = _lib.load()
     x = nhwc(x)
     B, C, H, W = x.shape
-    O, I = w.shape[:2]
-    so, si, sky, skx = w.stride()
-    R, Cc, sr, sc = (O, I, so, si) if rows_are_out else (I, O, si, so)
-    assert R <= cout_act and Cc <= C, (R, cout_act, Cc, C)
+    R, Cc, sr, sc, sky, skx = _weight_view(w, rows_are_out, cout_act, C)
+    mode = winograd_mode("fwd", cout_act)
 
-    # bf16x3: the GEMM's 128-wide N tile wants full tiles; other channel counts stay on the native GEMM (GIF_WINO_X3=0: A/B)
-    x3 = WINOGRAD_X3 and split_mode() and cout_act % 128 == 0
+    def build():  # f16x2: its transform and the bf16x3 transform (the operand of the GEMM's guarded bf16x3 twin) in one launch
+        RP, CP = _dims(lib.gif_winograd_pack_dims if mode == "native" else lib.gif_winograd_pack_dims_x3, cout_act, C, "winograd_pack_dims")
+        U = [torch.empty((lib.gif_winograd_weight_f32h2_bytes(RP, CP),), device=x.device, dtype=torch.uint8)] if mode == "f16x2" else []
+        U.append(torch.empty((16, RP, CP), device=x.device, dtype=torch.float32) if mode == "native" else
+                 torch.empty((16, 3, RP, CP), device=x.device, dtype=torch.bfloat16))
+        _call("winograd_weight", mode, w.data_ptr(), *[u.data_ptr() for u in U], R, Cc, RP, CP, sr, sc, sky, skx, 0 if rows_are_out else 1,
+              float(wscale), _stream())
+        return tuple(U) if mode == "f16x2" else U[0]
 
-    h2 = x3 and H2_WINO and get_fp32_mfma_mode() == "f16x2"
-
-    def build():
-        RP, CP = ctypes.c_int(), ctypes.c_int()
-        dims = lib.gif_winograd_pack_dims_x3 if x3 else lib.gif_winograd_pack_dims
-        _lib.check(dims(cout_act, C, ctypes.byref(RP), ctypes.byref(CP)), "winograd_pack_dims")
-        if h2:  # the f16x2 transform and the bf16x3 transform (the guarded fallback's operand) in one launch
-            U2 = torch.empty((lib.gif_winograd_weight_f32h2_bytes(RP.value, CP.value),), device=x.device, dtype=torch.uint8)
-            U3 = torch.empty((16, 3, RP.value, CP.value), device=x.device, dtype=torch.bfloat16)
-            _lib.check(lib.gif_winograd_weight_f32h2(w.data_ptr(), U2.data_ptr(), U3.data_ptr(), R, Cc, RP.value, CP.value, sr, sc, sky, skx,
-                                                     0 if rows_are_out else 1, float(wscale), _stream()), "winograd_weight_f32h2")
-            return U2, U3
-        if x3:
-            U = torch.empty((16, 3, RP.value, CP.value), device=x.device, dtype=torch.bfloat16)
-            fn = lib.gif_winograd_weight_f32x3
-        else:
-            U = torch.empty((16, RP.value, CP.value), device=x.device, dtype=torch.float32)
-            fn = lib.gif_winograd_weight_f32
-        _lib.check(fn(w.data_ptr(), U.data_ptr(), R, Cc, RP.value, CP.value, sr, sc, sky, skx, 0 if rows_are_out else 1, float(wscale),
-                      _stream()), "winograd_weight")
-        return U
-
-    U = _cached_weight_op(w, ("wino", rows_are_out, cout_act, C, float(wscale), x3, h2), build)
+    U = _cached_weight_op(w, ("wino", rows_are_out, cout_act, C, float(wscale), mode), build)
     V = torch.empty((lib.gif_winograd_workspace_floats(B, H, W, C),), device=x.device, dtype=torch.float32)
     out = empty_nhwc(B, cout_act, H, W, x.device)
     e = _epilogue(out_bchw=(B, cout_act, H, W), **epi)
-    if h2:  # f16x2 GEMM + its guarded bf16x3 twin
-        U2, U3 = U
-        _lib.check(lib.gif_conv3x3_winograd_f32h2(x.data_ptr(), U2.data_ptr(), U3.data_ptr() if H2_GUARD else None, out.data_ptr(),
-                                                  V.data_ptr(), B, H, W, C, cout_act, ctypes.byref(e), _stream()), "conv3x3_winograd_f32h2")
-        return (out, V) if keep_v else out
-    fn = lib.gif_conv3x3_winograd_f32x3 if x3 else lib.gif_conv3x3_winograd_f32
-    _lib.check(fn(x.data_ptr(), U.data_ptr(), out.data_ptr(), V.data_ptr(), B, H, W, C, cout_act, ctypes.byref(e), _stream()),
-               "conv3x3_winograd")
+    _call("conv3x3_winograd", mode, x.data_ptr(), *_weight_ptrs(U), out.data_ptr(), V.data_ptr(), B, H, W, C, cout_act, ctypes.byref(e), _stream())
     return (out, V) if keep_v else out
 
 
@@ -418,6 +441,21 @@ def _epi_check(x, epi):
     r = epi.get("residual")
     if r is not None:
         _same_dtype(x, r, "conv epilogue residual")
+
+
+def _conv_direct(plan: ConvPlan, op: str, src, w, out_bchw, g, wscale, epi):
+    """The direct-kernel launch of conv_fwd (op "conv2d_fwd") / conv_bwd_data ("conv2d_bwd_data") as `plan` says: weights packed for the
+    plan's mode (an f16x2 launch takes the bf16x3 packing for its guarded fallback too), then the one entry point."""
+    fwd, dt = op == "conv2d_fwd", src.dtype
+    if plan.mode == "f16x2":
+        wp = pack_weight_h2x3(w, fwd, out_bchw[1], src.shape[1], wscale, tapdense=plan.dense)
+    else:
+        wp = pack_weight(w, fwd, out_bchw[1], src.shape[1], wscale, dt, x3=plan.mode == "bf16x3", tapdense=plan.dense)
+    # out_f32 (f16 activations only): fp32 result, e.g. the RGB image of ToRGB
+    out = empty_nhwc(*out_bchw, src.device, torch.float32 if epi.get("out_f32") else dt)
+    e = _epilogue(out_bchw=out_bchw, dtype=dt, **epi)
+    _call(op, plan.mode, src.data_ptr(), *_weight_ptrs(wp), out.data_ptr(), ctypes.byref(g), ctypes.byref(e), _stream(), dense=plan.dense)
+    return out
 
 
 def conv_fwd(big, w, spec: ConvSpec, wscale=1.0, keep_v=False, **epi):
@@ -428,32 +466,16 @@ def conv_fwd(big, w, spec: ConvSpec, wscale=1.0, keep_v=False, **epi):
     big = nhwc(big)
     dt = big.dtype
     B, Cb, Hb, Wb = big.shape
-    O = w.shape[0]
-    Cs = cpad(O, dt)
+    Cs = cpad(w.shape[0], dt)
     Hs, Ws = spec.small_hw(Hb, Wb)
     _epi_check(big, epi)
     if dt != torch.float16:
         epi.pop("out_f32", None)  # (fp32 activations: the result is fp32 anyway)
-    if winograd_eligible(spec, B, Hb, Wb, Cb, Cs, dtype=dt):
+    plan = conv_plan("fwd", dt, B, spec, (Hb, Wb), (Hs, Ws), Cb, Cs, epi, big.numel() * big.element_size())
+    if plan.route == "winograd":
         return conv3x3_winograd(big, w, True, Cs, wscale, keep_v=keep_v, **epi)
-    if keep_v:
-        return conv_fwd(big, w, spec, wscale, **epi), None
-    x3 = x3_conv(dt, Cb, big, spec)
-    dense = x3_tapdense(dt, Cb, spec, False, epi, Cs) and big.numel() * 4 <= X3_MAX_INPUT_BYTES
-    h2 = h2_conv(x3, dense)
-    wp = None if h2 else pack_weight(w, True, Cs, Cb, wscale, dt, x3=x3, tapdense=dense)
-    # out_f32 (f16 activations only): fp32 result, e.g. the RGB image of ToRGB
-    out = empty_nhwc(B, Cs, Hs, Ws, big.device, torch.float32 if epi.get("out_f32") else dt)
-    g = _geom(B, Hb, Wb, Cb, Hs, Ws, Cs, spec)
-    e = _epilogue(out_bchw=(B, Cs, Hs, Ws), dtype=dt, **epi)
-    if h2:  # f16x2 kernels + the bf16x3 packing for their guarded fallback
-        wp2, wp = pack_weight_h2x3(w, True, Cs, Cb, wscale, tapdense=dense)
-        _lib.check((_lib.load().gif_conv2d_fwd_f32h2_tapdense if dense else _lib.load().gif_conv2d_fwd_f32h2)(big.data_ptr(), wp2.data_ptr(), wp.data_ptr() if H2_GUARD else None, out.data_ptr(), ctypes.byref(g),
-                                                    ctypes.byref(e), _stream()), "conv2d_fwd_f32h2")
-        return out
-    fn = _lib.load().gif_conv2d_fwd_f32x3_tapdense if dense else _lib.load().gif_conv2d_fwd_f32x3 if x3 else _fn("conv2d_fwd", dt)
-    _lib.check(fn(big.data_ptr(), wp.data_ptr(), out.data_ptr(), ctypes.byref(g), ctypes.byref(e), _stream()), "conv2d_fwd")
-    return out
+    out = _conv_direct(plan, "conv2d_fwd", big, w, (B, Cs, Hs, Ws), _geom(B, Hb, Wb, Cb, Hs, Ws, Cs, spec), wscale, epi)
+    return (out, None) if keep_v else out
 
 
 def conv_bwd_data(small, w, spec: ConvSpec, big_hw, wscale=1.0, **epi):
@@ -461,28 +483,13 @@ def conv_bwd_data(small, w, spec: ConvSpec, big_hw, wscale=1.0, **epi):
     small = nhwc(small)
     dt = small.dtype
     B, Cs, Hs, Ws = small.shape
-    I = w.shape[1]
-    Cb = cpad(I, dt)
+    Cb = cpad(w.shape[1], dt)
     Hb, Wb = big_hw
     _epi_check(small, epi)
-    if (Hb, Wb) == (Hs, Ws) and winograd_eligible(spec, B, Hs, Ws, Cs, Cb, dtype=dt):
+    plan = conv_plan("dgrad", dt, B, spec, (Hb, Wb), (Hs, Ws), Cs, Cb, epi, small.numel() * small.element_size())
+    if plan.route == "winograd":
         return conv3x3_winograd(small, w, False, Cb, wscale, **epi)
-    x3 = x3_conv(dt, Cs, small, spec)
-    dense = x3_tapdense(dt, Cs, spec, True, epi, Cb) and small.numel() * 4 <= X3_MAX_INPUT_BYTES
-    h2 = h2_conv(x3, dense)
-    wp = None if h2 else pack_weight(w, False, Cb, Cs, wscale, dt, x3=x3, tapdense=dense)
-    out = empty_nhwc(B, Cb, Hb, Wb, small.device, dt)
-    g = _geom(B, Hb, Wb, Cb, Hs, Ws, Cs, spec)
-    e = _epilogue(out_bchw=(B, Cb, Hb, Wb), dtype=dt, **epi)
-    if h2:
-        wp2, wp = pack_weight_h2x3(w, False, Cb, Cs, wscale, tapdense=dense)
-        _lib.check((_lib.load().gif_conv2d_bwd_data_f32h2_tapdense if dense else _lib.load().gif_conv2d_bwd_data_f32h2)(small.data_ptr(), wp2.data_ptr(), wp.data_ptr() if H2_GUARD else None, out.data_ptr(), ctypes.byref(g),
-                                                         ctypes.byref(e), _stream()), "conv2d_bwd_data_f32h2")
-        return out
-    fn = (_lib.load().gif_conv2d_bwd_data_f32x3_tapdense if dense else _lib.load().gif_conv2d_bwd_data_f32x3 if x3
-          else _fn("conv2d_bwd_data", dt))
-    _lib.check(fn(small.data_ptr(), wp.data_ptr(), out.data_ptr(), ctypes.byref(g), ctypes.byref(e), _stream()), "conv2d_bwd_data")
-    return out
+    return _conv_direct(plan, "conv2d_bwd_data", small, w, (B, Cb, Hb, Wb), _geom(B, Hb, Wb, Cb, Hs, Ws, Cs, spec), wscale, epi)
 
 
 def pad32(c: int) -> int:
@@ -499,8 +506,7 @@ def conv3x3_winograd_wgrad(small, big, O, I, wscale=1.0, small_scale=None, big_s
     B, Cs, H, W = small.shape
     Cb = big.shape[1]
     assert big.shape == (B, Cb, H, W) and O <= Cs and I <= Cb
-    RP, CP = ctypes.c_int(), ctypes.c_int()
-    _lib.check(lib.gif_conv2d_wgrad_dims(pad32(Cs), pad32(Cb), ctypes.byref(RP), ctypes.byref(CP)), "wgrad_dims")
+    RP, CP = _dims(lib.gif_conv2d_wgrad_dims, pad32(Cs), pad32(Cb), "wgrad_dims")
     nsplit = lib.gif_conv3x3_winograd_wgrad_splits(B, H, W, Cs, Cb)
     dev = small.device
     nv = lib.gif_winograd_workspace_floats(B, H, W, Cb)
@@ -508,16 +514,13 @@ def conv3x3_winograd_wgrad(small, big, O, I, wscale=1.0, small_scale=None, big_s
         raise _lib.GifHipError(f"conv3x3_winograd_wgrad: cached V has {big_v.numel()} floats, expected {nv}")
     V = big_v if big_v is not None else torch.empty((nv,), device=dev, dtype=torch.float32)
     Mg = torch.empty((lib.gif_winograd_workspace_floats(B, H, W, Cs),), device=dev, dtype=torch.float32)
-    ws = torch.empty((nsplit, 16, RP.value, CP.value), device=dev, dtype=torch.float32)
-    fn = (lib.gif_conv3x3_winograd_wgrad_f32h2 if (H2_WGRAD and get_fp32_mfma_mode() == "f16x2") else
-          lib.gif_conv3x3_winograd_wgrad_f32x3 if split_mode() else lib.gif_conv3x3_winograd_wgrad_f32)
-    _lib.check(fn(None if big_v is not None else big.data_ptr(), small.data_ptr(), V.data_ptr(), Mg.data_ptr(), ws.data_ptr(),
-                                                  _p(small_scale), _p(big_scale), B, H, W, Cs, Cb, nsplit, _stream()),
-               "conv3x3_winograd_wgrad")
+    ws = torch.empty((nsplit, 16, RP, CP), device=dev, dtype=torch.float32)
+    _call("conv3x3_winograd_wgrad", winograd_mode("wgrad", Cs), None if big_v is not None else big.data_ptr(), small.data_ptr(), V.data_ptr(),
+          Mg.data_ptr(), ws.data_ptr(), _p(small_scale), _p(big_scale), B, H, W, Cs, Cb, nsplit, _stream())
     dw = torch.empty((O, I, 3, 3), device=dev, dtype=torch.float32)
     so, si, sky, skx = dw.stride()
-    _lib.check(lib.gif_winograd_unpack_wgrad_f32(ws.data_ptr(), dw.data_ptr(), nsplit, O, I, RP.value, CP.value, so, si, sky,
-                                                 skx, float(wscale), _stream()), "winograd_unpack_wgrad")
+    _lib.check(lib.gif_winograd_unpack_wgrad_f32(ws.data_ptr(), dw.data_ptr(), nsplit, O, I, RP, CP, so, si, sky, skx, float(wscale),
+                                                 _stream()), "winograd_unpack_wgrad")
     return dw
 
 
@@ -527,31 +530,23 @@ def conv_wgrad(small, big, spec: ConvSpec, O, I, wscale=1.0, small_scale=None, b
     lib = _lib.load()
     small, big = nhwc(small), nhwc(big)
     _same_dtype(small, big, "conv_wgrad")
-    dt = small.dtype
-    f16 = dt == torch.float16
     B, Cs, Hs, Ws = small.shape
     _, Cb, Hb, Wb = big.shape
     assert O <= Cs and I <= Cb
-    if (WINOGRAD_WGRAD and (Hb, Wb) == (Hs, Ws) and Cs >= 64 and Cb >= 64
-            and winograd_eligible(spec, B, Hs, Ws, Cb, Cs, min(WINOGRAD_MIN_TILES, WINOGRAD_WGRAD_MIN_TILES), dtype=dt,
-                                  min_c=_winograd_min_c(WINOGRAD_WGRAD_MIN_C))):
+    plan = conv_plan("wgrad", small.dtype, B, spec, (Hb, Wb), (Hs, Ws), Cb, Cs)
+    if plan.route == "winograd":
         return conv3x3_winograd_wgrad(small, big, O, I, wscale, small_scale, big_scale, big_v)
     g = _geom(B, Hb, Wb, Cb, Hs, Ws, Cs, spec)
-    RP, CP = ctypes.c_int(), ctypes.c_int()
-    dims, splits = ((lib.gif_conv2d_wgrad_dims_f16, lib.gif_conv2d_wgrad_splits_f16) if f16 else
-                    (lib.gif_conv2d_wgrad_dims, lib.gif_conv2d_wgrad_splits))
-    _lib.check(dims(Cs, Cb, ctypes.byref(RP), ctypes.byref(CP)), "wgrad_dims")
-    nsplit = splits(ctypes.byref(g))
-    T = spec.KH * spec.KW
-    ws = torch.empty((nsplit, T, RP.value, CP.value), device=small.device, dtype=torch.float32)
-    fn = (lib.gif_conv2d_wgrad_f32h2 if (not f16 and H2_WGRAD and get_fp32_mfma_mode() == "f16x2") else
-          lib.gif_conv2d_wgrad_f32x3 if (not f16 and split_mode()) else _fn("conv2d_wgrad", dt))
-    _lib.check(fn(small.data_ptr(), big.data_ptr(), ws.data_ptr(), _p(small_scale), _p(big_scale), ctypes.byref(g), nsplit, _stream()),
-               "conv2d_wgrad")
+    f16 = "_f16" if plan.mode == "f16" else ""
+    RP, CP = _dims(getattr(lib, "gif_conv2d_wgrad_dims" + f16), Cs, Cb, "wgrad_dims")
+    nsplit = getattr(lib, "gif_conv2d_wgrad_splits" + f16)(ctypes.byref(g))
+    ws = torch.empty((nsplit, spec.KH * spec.KW, RP, CP), device=small.device, dtype=torch.float32)
+    _call("conv2d_wgrad", plan.mode, small.data_ptr(), big.data_ptr(), ws.data_ptr(), _p(small_scale), _p(big_scale), ctypes.byref(g), nsplit,
+          _stream())
     dw = torch.empty((O, I, spec.KH, spec.KW), device=small.device, dtype=torch.float32)
     so, si, sky, skx = dw.stride()
-    _lib.check(lib.gif_unpack_wgrad_f32(ws.data_ptr(), dw.data_ptr(), nsplit, O, I, spec.KH, spec.KW, RP.value, CP.value,
-                                        so, si, sky, skx, float(wscale), _stream()), "unpack_wgrad")
+    _lib.check(lib.gif_unpack_wgrad_f32(ws.data_ptr(), dw.data_ptr(), nsplit, O, I, spec.KH, spec.KW, RP, CP, so, si, sky, skx, float(wscale),
+                                        _stream()), "unpack_wgrad")
     return dw
 
 

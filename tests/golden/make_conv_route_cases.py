@@ -3,8 +3,8 @@ library call gif_amd/ops.py makes for it when the call ends in csrc/conv_igemm.h
 line per case:
     <row>-<mode>  fwd|dgrad  native|bf16x3|f16x2|f16  dense scaled dot  B Cin Cout K stride pad H W
 (the forward convolution, channel counts as the activations carry them; dense / scaled / dot: tap-dense entry point, per-sample input
-scales, dot fusion).  The decisions are ops.winograd_eligible, x3_conv, x3_tapdense and h2_conv, which are pure Python: no GPU and no
-library is needed.  tests/host/conv_route_dump.cpp reads the file; tests/test_conv_route.py checks that it is current.
+scales, dot fusion).  The decision is ops.conv_plan, the function conv_fwd and conv_bwd_data ask themselves; it is pure Python: no GPU and
+no library is needed.  tests/host/conv_route_dump.cpp reads the file; tests/test_conv_route.py checks that it is current.
 Run: python tests/golden/make_conv_route_cases.py"""
 import os
 import sys
@@ -37,19 +37,12 @@ def case_lines():
                 try:
                     cb, cs = routes.cpad(Ci, f16), routes.cpad(Co, f16)
                     epi = {"in_scale": True} if row.epi in ("full", "scale") else {}
-                    if row.op == "fwd":
-                        wino = ops.winograd_eligible(spec, B, H, W, cb, cs, dtype=dt)
-                        cin, cout, hw_out = cb, cs, Hs * Ws
-                    else:
-                        wino = (H, W) == (Hs, Ws) and ops.winograd_eligible(spec, B, Hs, Ws, cs, cb, dtype=dt)
-                        cin, cout, hw_out = cs, cb, H * W
-                    if wino:
+                    cin, cout, hw_out = (cb, cs, Hs * Ws) if row.op == "fwd" else (cs, cb, H * W)
+                    plan = ops.conv_plan(row.op, dt, B, spec, (H, W), (Hs, Ws), cin, cout, epi)
+                    if plan.route == "winograd":
                         continue
-                    x3 = ops.x3_conv(dt, cin)
-                    dense = ops.x3_tapdense(dt, cin, spec, row.op == "dgrad", epi, cout)
-                    lib_mode = "f16" if f16 else "f16x2" if ops.h2_conv(x3, dense) else "bf16x3" if (x3 or dense) else "native"
                     dot = row.epi == "fuse" and hw_out % 256 == 0
-                    lines.append(f"{row.name}-{mode} {row.op} {lib_mode} {int(dense)} {int(bool(epi))} {int(dot)} {B} {cb} {cs} {K} {s} {p} {H} {W}")
+                    lines.append(f"{row.name}-{mode} {row.op} {plan.mode} {int(plan.dense)} {int(bool(epi))} {int(dot)} {B} {cb} {cs} {K} {s} {p} {H} {W}")
                 finally:
                     for k, v in saved:
                         setattr(ops, k, v)

@@ -2,7 +2,7 @@
 // One line per case:
 //   name | op | mode | flags | the forward conv's geometry -> packing, family, phases, zero fill, merged, partial rows x tile rows [, halo] : launches
 // (f16x2 cases: the route of the guarded bf16x3 twin after " + twin").  Cases: first the lines of the file given as the first argument
-// (tests/golden/conv_route_cases.txt: the library calls gif_amd/ops.py makes for the rows of tests/test_gpu_conv_routes.py), then a grid of
+// (tests/golden/conv_route_cases.txt: the library calls ops.conv_plan decides on for the rows of tests/test_gpu_conv_routes.py), then a grid of
 // its own that puts every predicate of the header on both sides of its threshold, all with the default knobs; then once per non-default
 // knob value over that grid, where only the cases are printed whose line differs from the default one (and how many of how many did).
 // tests/test_conv_route.py builds this with AddressSanitizer and UBSan (host code only), runs it and compares the output with

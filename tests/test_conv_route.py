@@ -12,7 +12,10 @@ a grid that puts every predicate of the header on both sides of its threshold, t
 CLAIMS restates, as data, what the comments of ROWS say about tile, launches, bulk rows and merged phases; the table must say the same.
 tests/golden/conv_queries_golden.json (make_conv_queries_golden.py) holds what gif_conv2d_pack_dims / _x3 / _f16, gif_conv2d_x3_eligible
 and gif_conv2d_f16_halo_eligible returned for the table's geometries at the commit before the header: the library must still return
-them, and the table's RP / CP / halo columns must agree."""
+them, and the table's RP / CP / halo columns must agree.
+tests/golden/conv_plan_table.txt (make_conv_plan_golden.py) holds what gif_amd/ops.py decided before it called the library (Winograd or
+direct route, contraction mode, tap-dense K order) at the commit before ops.conv_plan existed, over a grid that puts every rule and
+knob of that decision on both sides: conv_plan must still decide the same."""
 import json
 import os
 import re
@@ -25,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, GOLDEN)
 import make_conv_queries_golden as rec  # noqa: E402  (the geometry keys and the library queries of the recording)
+import make_conv_plan_golden as plans  # noqa: E402
 import make_conv_route_cases as cases  # noqa: E402
 
 
@@ -55,6 +59,20 @@ def test_route_table_matches_the_recorded_one(dump_lines):
 def test_case_file_is_current():
     with open(os.path.join(GOLDEN, "conv_route_cases.txt")) as f:
         assert f.read().splitlines() == cases.case_lines(), "run tests/golden/make_conv_route_cases.py"
+
+
+def test_conv_plan_decides_what_the_recorded_table_says():
+    with open(os.path.join(GOLDEN, "conv_plan_table.txt")) as f:
+        want = f.read().splitlines()
+    got = plans.table_lines()
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a == b, f"line {i + 1}:\n got  {a}\n want {b}"
+    assert len(got) == len(want) > 1000
+    # both sides of every answer are in the table, for each op
+    for op in ("fwd", "dgrad", "wgrad"):
+        ends = {l.split(" -> ")[1] for l in want if " -> " in l and l.split()[1] == op}
+        assert {"winograd native 0", "winograd bf16x3 0", "winograd f16x2 0", "direct native 0", "direct bf16x3 0", "direct f16x2 0", "direct f16 0"} <= ends, (op, ends)
+        assert (op == "wgrad") != ({"direct bf16x3 1", "direct f16x2 1"} <= ends), (op, ends)
 
 
 # ---- the claims of the ROWS comments ---------------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 """-m gpu: every convolution and FIR dispatch route on both sides of its threshold, against an fp64 reference of the same operation.
 
 The rest of the suite picks its shapes by model layer.  Here each row of the tables is a shape computed from a dispatch predicate
-(gif_amd/ops.py: winograd_eligible, x3_conv, x3_tapdense, h2_conv; csrc/conv_route.h: route_phase, conv_route, rows_thin_ok,
-halo_eligible; csrc/wgrad_route.h: small_wgrad_ok, wgrad_big_tile, the x3 / x3_thin tile rules of wgrad_route; csrc/elementwise.hip:
+(gif_amd/ops.py: conv_plan and the predicates it composes, winograd_eligible, x3_conv, x3_tapdense, h2_conv; csrc/conv_route.h:
+route_phase, conv_route, rows_thin_ok, halo_eligible; csrc/wgrad_route.h: small_wgrad_ok, wgrad_big_tile, the x3 / x3_thin tile rules of wgrad_route; csrc/elementwise.hip:
 upfirdn2d_impl, gif::reduce_partials): the last shape that takes a route and the first that does not.  Each row's comment names the
 predicate and the side.
 
