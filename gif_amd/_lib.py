@@ -69,6 +69,11 @@ PROTOTYPES = {
     "gif_vertex_normals_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
     "gif_vertex_normals_bwd_f32": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "gif_face_gather_bwd_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "gif_flame_skin_f32": (c_int, [P] * 7 + [c_int] * 4 + [P]),
+    "gif_flame_skin_bwd_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "gif_flame_skin_bwd_f32": (c_int, [P] * 7 + [c_int] * 4 + [P, P]),
+    "gif_flame_joints_f32": (c_int, [P, P, ctypes.POINTER(ctypes.c_int32), P, c_i64, c_int, P, c_i64, c_int, P, c_i64, P, c_i64, P, c_i64,
+                                     P, P, c_int, c_int, c_int, P]),
     "gif_texture_map_f32": (c_int, [P] * 9 + [c_int] * 6 + [P]),
     "gif_texture_map_bwd_f32": (c_int, [P] * 8 + [c_int] * 6 + [P]),
     "gif_conv_epilogue_ws_floats": (c_i64, [c_i64, c_int]),

@@ -5,8 +5,10 @@ Mirrors the pieces of the reference that exist in-tree:
   NDC -> pixel transform, buffer init    my_utils/standard_rasterize_cuda/visibility.py:38-44
   8-bit quantisation of the renders      my_utils/visualize_flame_overlay.py:29-31  (floor(clamp*255)/255)
   [-1,1] scaling and channel order       plots/generate_random_samples.py:22-30, :188-189  (cat(texture, normal))
-The FLAME layer and the spherical-harmonics texture shading live in the absent `photometric_optimization` submodule
-(parity unpinned, out of scope): the per-vertex "texture" attribute is therefore an INPUT here.
+The FLAME layer lives in the reference's absent `photometric_optimization` submodule; its algorithm is public and is built
+here as gif_amd.flame.FlameLayer (HIP forward and backward) — only the licensed model file stays outside.  The
+spherical-harmonics texture shading of that submodule is out of scope (parity unpinned): the per-vertex "texture" attribute
+is therefore an INPUT here.
 Kernels: gif_vertex_normals_f32 (gather, deterministic) and gif_rasterize_colors_f32, both behind the C ABI.
 Backward (differentiable condition rendering): gif_vertex_normals_bwd_f32, gif_rasterize_colors_bwd_f32 and
 gif_face_gather_bwd_f32, all deterministic (no float atomics).
@@ -200,8 +202,10 @@ def render_condition(vertices_ndc, faces, vertex_texture, h=256, w=256, straight
 class FlameConditionRenderer:
     """callable flame_batch [N, >=159] -> (rend_flm, norma_map_img), both [N,3,h,w] in [-1,1]: the role
     OverLayViz.get_rendered_mesh + the [-1,1] scaling play in InterpolatedTextureLoss.get_image_and_textures
-    (loss_functions/losses.py:184-215).  `flame` is the FLAME layer (absent submodule: injected; gif_amd.data.SyntheticFlame for
-    synthetic runs), `vertex_texture` [V,3] in [0,1] replaces the SH-lit albedo render (out of scope)."""
+    (loss_functions/losses.py:184-215).  `flame` is the FLAME layer: gif_amd.flame.FlameLayer over a converted model file or
+    over flame.synthetic_flame_model (differentiable with respect to shape, expression and pose), any callable with its
+    signature, or gif_amd.data.SyntheticFlame, the benchmark's fixed stand-in.  `vertex_texture` [V,3] in [0,1] replaces the
+    SH-lit albedo render (out of scope)."""
 
     def __init__(self, flame, faces, vertex_texture, h=256, w=256, straight_through=False):
         self.flame, self.faces, self.vertex_texture, self.h, self.w = flame, faces, vertex_texture, h, w

@@ -192,6 +192,39 @@ int gif_vertex_normals_bwd_f32(const float* verts, const int32_t* faces, const i
 int gif_face_gather_bwd_f32(const float* grad_face, const int32_t* csr_off, const int32_t* csr_ent, float* grad_vertex,
                             int B, int V, int F, gif_stream_t stream);
 
+/* The FLAME layer (blend shapes, pose correctives, linear blend skinning).  The published algorithm in the smplx
+ * formulation; the reference keeps its layer in an absent submodule, so there is no line to cite.  Constants of a model with V
+ * vertices, K = n_shape + n_exp blend shapes, J <= 8 joints, P = 9 (J - 1) pose correctives, KP = K + P:
+ *   tmpl [3V]; dirs [KP][3V] (k-major: the K blend-shape rows, then the P corrective rows); lbs_w [V][J];
+ *   J0 [J][3] = J_regressor . v_template and Jdirs [K][3J] = J_regressor . shapedirs (joints are linear in betas).
+ * Per sample: coef [KP] = cat(betas, pose_feature), A [J][12] = the chain's relative transforms, row-major 3x4.
+ *
+ * gif_flame_skin_f32: v_posed = tmpl + dirs^T coef; verts[v] = (sum_j lbs_w[v,j] A_j) [v_posed[v], 1].  verts, v_posed [B][3V];
+ * v_posed may be null (the backward reads it).  B = 0 or V = 0: no-op.  J outside 1..8 or KP < P: GIF_EINVAL.
+ *
+ * gif_flame_skin_bwd_f32: g_verts [B][3V] = dL/d verts ->
+ *   g_coef [B][KP] = dirs . g_v_posed, with g_v_posed[b,v] = (sum_j lbs_w[v,j] A[b,j].R)^T g_verts[b,v]
+ *   g_A [B][J][12] = sum_v lbs_w[v,j] g_verts[b,v] (x) [v_posed[b,v], 1]
+ * Either output may be null (not computed; g_coef alone needs no v_posed, g_A alone needs neither dirs nor A).  Both are
+ * reductions over V: per-workgroup partial sums in `workspace` (gif_flame_skin_bwd_workspace_bytes(B, V, KP, J) bytes, 4-byte
+ * aligned, no initialisation needed), then a fixed-order sum: no float atomics, run-to-run identical bits.  The constants
+ * receive no gradient.
+ *
+ * gif_flame_joints_f32: everything in front of the skinning for inputs that need no gradient.  shape [B][n_shape], expr
+ * [B][n_exp], pose [B][6] (global, jaw), neck [B][3], eye [B][6]: axis-angle, row strides ld_* in floats, each may be null
+ * (zeros).  Joint order: global, neck, jaw, left eye, right eye; joints past the fifth do not rotate.  parents [J] is a HOST
+ * array, parents[j] < j (checked).  Writes coef [B][KP] (betas, then R_1..R_{J-1} - I with R = Rodrigues in the smplx form,
+ * angle = |r + 1e-8|) and A [B][J][12]. */
+int gif_flame_skin_f32(const float* tmpl, const float* dirs, const float* lbs_w, const float* coef, const float* A,
+                       float* verts, float* v_posed, int B, int V, int KP, int J, gif_stream_t stream);
+int64_t gif_flame_skin_bwd_workspace_bytes(int B, int V, int KP, int J);
+int gif_flame_skin_bwd_f32(const float* dirs, const float* lbs_w, const float* A, const float* g_verts, const float* v_posed,
+                           float* g_coef, float* g_A, int B, int V, int KP, int J, void* workspace, gif_stream_t stream);
+int gif_flame_joints_f32(const float* J0, const float* Jdirs, const int32_t* parents, const float* shape, int64_t ld_shape,
+                         int n_shape, const float* expr, int64_t ld_expr, int n_exp, const float* pose, int64_t ld_pose,
+                         const float* neck, int64_t ld_neck, const float* eye, int64_t ld_eye, float* A, float* coef, int B,
+                         int KP, int J, gif_stream_t stream);
+
 /* Texture stealing — replaces FlameTextureSpace.compute_texture_map (model/stg2_generator.py:378-421):
  * per (sample, UV texel) barycentric 3-D point -> orthographic projection (y flipped) -> bilinear fetch of the source image
  * (grid_sample, zero padding, align_corners=False), and the normal-z visibility mask.  img [B,C,H,W] NCHW; verts/normals
