@@ -15,6 +15,8 @@ Two families:
   * BilinearDownFn — the condition pyramid; _TextureMapFn lives in gif_amd/texture_space.py.
 All tensors are logical NCHW with NHWC memory (ops.nhwc).
 """
+import weakref
+
 import torch
 from torch.autograd import Function
 
@@ -36,16 +38,48 @@ from .ops import ConvSpec
 # three full-resolution tensors per layer).  Gradients from consumers that do not know the protocol arrive on y as before and
 # take the stand-alone pass; both add up.  Under create_graph (R1, the path-length / direct-gradient regularisers) consumers
 # return the plain, differentiable gradient on y and leave the port alone: a port only ever carries first-order gradients.
+#
+# Someone who LOOKS at the gradient of y must see all of it.  A consumer does not take the port of a tensor that retains its
+# gradient or carries backward hooks when the consumer is built (_take_port), and a consumer that did take it checks again when its
+# backward runs (_port_live): retain_grad() or a hook registered after the forward sends that pass through the stand-alone route, on
+# y.  `parts` only ever holds contributions of the backward pass that is running: whoever files one queues an engine callback that
+# empties the list when the pass ends (_file_part), so a pass in which the producer is pruned (autograd.grad w.r.t. a downstream weight
+# only) leaves nothing behind for the next pass over a retained graph.
+# LIMITATION: torch.autograd.grad(..., inputs=[y]) w.r.t. a tagged activation itself cannot be seen by the consumers.  It finds only
+# what reached y from consumers outside the protocol: the engine's "appears to not have been used" error (None under
+# allow_unused=True) when there are none.  Call y.retain_grad(), register a hook, or run with GIF_FUSE_GRAD=0 to inspect such a gradient.
 class ActPort:
-    __slots__ = ("alias", "slope", "gain", "want_bias", "parts")
+    __slots__ = ("alias", "slope", "gain", "want_bias", "parts", "y_ref")
 
     def __init__(self, slope, gain, want_bias):
         self.alias, self.slope, self.gain, self.want_bias = None, float(slope), float(gain), bool(want_bias)
         self.parts = []  # [C] bias-gradient contributions appended by the consumers' backward passes
+        self.y_ref = None  # weak reference to the tagged output y (_tag)
 
     def cfg(self):
-        """What a consumer's backward needs (no reference to the alias: the autograd node must not own a cycle)."""
-        return (self.slope, self.gain, self.want_bias, self.parts)
+        """What a consumer's backward needs (no reference to the alias or to y: the autograd node must not own a cycle)."""
+        return (self.slope, self.gain, self.want_bias, self.parts, self.y_ref)
+
+
+def _observed(t):
+    """Somebody will look at the gradient that arrives on t: it retains its gradient or carries backward hooks."""
+    return t.retains_grad or bool(t._backward_hooks)
+
+
+def _port_live(cfg):
+    """The port a consumer took at forward time may still be served in the backward pass that is running."""
+    if cfg is None:
+        return False
+    y = cfg[4]() if cfg[4] is not None else None
+    return y is None or not _observed(y)
+
+
+def _file_part(parts, part):
+    """Append a bias-gradient contribution for the producer.  The list is emptied when the running backward pass ends, whether or not
+    the producer ran in it."""
+    if not parts:
+        torch.autograd.Variable._execution_engine.queue_callback(parts.clear)
+    parts.append(part)
 
 
 def _take_port(x, identity=False):
@@ -53,7 +87,7 @@ def _take_port(x, identity=False):
     serve: False = a real activation (mask in the gradient kernel's epilogue), True = bias-only layers (residual inputs)."""
     port = getattr(x, "_gif_port", None)
     if (port is None or not ops.FUSE_GRAD or not torch.is_grad_enabled() or port.alias is None or not port.alias.requires_grad
-            or (port.slope == 1.0 and port.gain == 1.0) != identity):
+            or (port.slope == 1.0 and port.gain == 1.0) != identity or _observed(x)):
         return None, None
     return port.alias, port.cfg()
 
@@ -90,12 +124,13 @@ def _need(ctx, i):
 
 def _port_on(ctx):
     """This backward delivers to the input's port (first-order pass) instead of to the input itself."""
-    return ctx.in_port is not None and not torch.is_grad_enabled()
+    return ctx.in_port is not None and not torch.is_grad_enabled() and _port_live(ctx.in_port)
 
 
 def _tag(y, alias, port):
     if port is not None:
         port.alias = alias
+        port.y_ref = weakref.ref(y)
         y._gif_port = port
     return y
 
@@ -114,18 +149,18 @@ def _deliver_residual(r_port, gpre, gb):
     """A layer's `residual` input is the output of an identity-activation layer (the last condition-noise conv: conv + bias):
     its gradient IS this layer's pre-activation gradient gpre, and its bias gradient is the same column sum gb this layer takes
     for its own bias — both are handed over (first-order passes) instead of the producer launching a column-sum pass over gpre."""
-    _, _, want_b, parts = r_port
+    want_b, parts = r_port[2:4]
     if want_b:
-        parts.append(gb if gb is not None else ops.colsum(gpre))
+        _file_part(parts, gb if gb is not None else ops.colsum(gpre))
     return gpre
 
 
 def _mask_into_port(cfg, gx, x):
     """Stand-alone form of a consumer's duty (differentiable to any order): mask gx with the activation of x, file the bias part."""
-    slope, gain, want_b, parts = cfg
+    slope, gain, want_b, parts = cfg[:4]
     gxm, gb = BiasActBwdFn.apply(gx, x, want_b, slope, gain)
     if want_b:
-        parts.append(gb)
+        _file_part(parts, gb)
     return gxm
 
 
@@ -256,11 +291,11 @@ def _conv_dgrad(gpre, w, spec, big_hw, ws, residual, in_port, x):
     that produced x, and the bias-gradient column sums are taken, in the kernel's epilogue."""
     if in_port is None:
         return Conv2dFn.apply(gpre, w, spec, True, big_hw, ws, residual)
-    slope, gain, want_b, parts = in_port
+    slope, gain, want_b, parts = in_port[:4]
     fuse = ops.GradFuse(mask_src=x, mask_slope=slope, mask_gain=gain, want_colsum=want_b)
     gx = ops.conv_bwd_data(gpre, w, spec, big_hw, ws, residual=None if residual is None else ops.nhwc(residual), fuse=fuse)
     if want_b:
-        parts.append(fuse.colsum)
+        _file_part(parts, fuse.colsum)
     return gx
 
 
@@ -565,14 +600,14 @@ class Upfirdn2dFn(Function):
         if not _port_on(ctx):
             return Upfirdn2dFn.apply(gy, k, down, up, k.shape[0] - 1 - pad0, in_hw, not flip), None, None, None, None, None, None, None, None
         x = ctx.saved_tensors[1]
-        slope, gain, want_b, parts = ctx.in_port
+        slope, gain, want_b, parts = ctx.in_port[:4]
         if not ops.fir_fusable(x.shape[1], down, up, k.shape, x.dtype):
             gx = _mask_into_port(ctx.in_port, Upfirdn2dFn.apply(gy, k, down, up, k.shape[0] - 1 - pad0, in_hw, not flip), x)
         else:
             fuse = ops.GradFuse(mask_src=x, mask_slope=slope, mask_gain=gain, want_colsum=want_b)
             gx = ops.upfirdn2d(ops.nhwc(gy), k, down, up, k.shape[0] - 1 - pad0, in_hw, not flip, fuse=fuse)
             if want_b:
-                parts.append(fuse.colsum)
+                _file_part(parts, fuse.colsum)
         return None, None, None, None, None, None, None, None, gx
 
 
@@ -603,7 +638,7 @@ class BlurBiasActFn(Function):
         if gpre is not None and ctx.needs_input_grad[0]:
             gx = Upfirdn2dFn.apply(gpre, k, 1, 1, k.shape[0] - 1 - pad0, in_hw, False)
         if gpre is not None and has_res and ctx.needs_input_grad[4]:
-            if ctx.r_port is not None and not torch.is_grad_enabled():
+            if not torch.is_grad_enabled() and _port_live(ctx.r_port):
                 gra = _deliver_residual(ctx.r_port, gpre, gb)
             else:
                 gr = gpre
@@ -803,16 +838,18 @@ def _modconv_dgrad_fused(g, w, spec, tr, x, s, d, ws, in_port, want_gs):
     convolution of d * g with the modulation s as its output scale, gs as a dot product against x and — with in_port — the
     backward of the leaky ReLU that produced x, all in the kernel's epilogue (ops.GradFuse).  Replaces data gradient -> dxs,
     mul_reduce(dxs, x) -> (gs, s * dxs) [three full-resolution tensors] and the activation's own backward pass [three more]."""
-    slope, gain, want_b, parts = in_port if in_port is not None else (1.0, 1.0, False, None)
-    fuse = ops.GradFuse(mask_src=x if in_port is not None else None, mask_slope=slope, mask_gain=gain, want_colsum=want_b,
-                        dot_src=x if want_gs else None)
+    slope, gain, want_b, parts = in_port[:4] if in_port is not None else (1.0, 1.0, False, None)
+    fuse = None  # (neither a mask nor a modulation gradient to take, e.g. a frozen mapping network: the plain launch)
+    if in_port is not None or want_gs:
+        fuse = ops.GradFuse(mask_src=x if in_port is not None else None, mask_slope=slope, mask_gain=gain, want_colsum=want_b,
+                            dot_src=x if want_gs else None)
     if not tr:
         gx = ops.conv_bwd_data(g, w, spec, tuple(x.shape[2:]), ws, in_scale=d, out_scale=s, fuse=fuse)
     else:
         gx = ops.conv_fwd(g, w, spec, ws, in_scale=d, out_scale=s, fuse=fuse)
     if want_b:
-        parts.append(fuse.colsum)
-    return gx, fuse.dot
+        _file_part(parts, fuse.colsum)
+    return gx, (None if fuse is None else fuse.dot)
 
 
 class ModConvFn(Function):
@@ -852,7 +889,8 @@ class ModConvFn(Function):
                 (x, w, s, d), tuple(_need(ctx, i) for i in range(4)), gy,
                 lambda x_, w_, s_, d_: _modconv_composite(x_, w_, s_, d_, spec, tr, ctx.out_hw, ws))
             return gx, gw, gs, gd, None, None, None, None, None, None, None
-        port = ctx.in_port is not None
+        in_port = ctx.in_port if _port_live(ctx.in_port) else None
+        port = in_port is not None
         if gy.dtype != x.dtype:  # fp32 result of an f16 layer (out_f32): its gradient re-enters the f16 kernels as f16
             gy = gy.to(x.dtype)
         x, s, gy = ops.nhwc(x), s.contiguous(), ops.nhwc(gy)
@@ -861,7 +899,7 @@ class ModConvFn(Function):
         gx = gs = gd = gw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
             if ops.dot_fusable(x.shape[2], x.shape[3], x.dtype):
-                gx, gs = _modconv_dgrad_fused(gy, w, spec, tr, x, s, d, ws, ctx.in_port, ctx.needs_input_grad[2])
+                gx, gs = _modconv_dgrad_fused(gy, w, spec, tr, x, s, d, ws, in_port, ctx.needs_input_grad[2])
             else:
                 # gradient w.r.t. (s*x): adjoint conv applied to d*gy (d enters as the input scale of the adjoint)
                 if not tr:
@@ -869,8 +907,8 @@ class ModConvFn(Function):
                 else:
                     dxs = ops.conv_fwd(gy, w, spec, ws, in_scale=d)
                 gs, gx = ops.mul_reduce(dxs, x, scale=s, want_scaled=True)
-                if ctx.in_port is not None:
-                    gx = _mask_into_port(ctx.in_port, gx, x)
+                if port:
+                    gx = _mask_into_port(in_port, gx, x)
         if _need(ctx, 1):
             if not tr:
                 gw = ops.conv_wgrad(gy, x, spec, O, I, ws, small_scale=d, big_scale=s, big_v=ctx.v)
@@ -924,7 +962,8 @@ class ModConvActFn(Function):
                 (x, w, s, d, residual, bias), tuple(_need(ctx, i) for i in range(6)), gy,
                 lambda x_, w_, s_, d_, r_, b_: _modconv_composite(x_, w_, s_, d_, spec, False, None, ws, r_, b_, (slope, gain)))
             return (gx, gw, gs, gd, gr, gb) + none9
-        port = ctx.in_port is not None
+        in_port = ctx.in_port if _port_live(ctx.in_port) else None
+        port = in_port is not None
         x, s, d = ops.nhwc(x), s.contiguous(), d.contiguous()
         residual = None if residual is None else ops.nhwc(residual)
         want_b = has_bias and _need(ctx, 5)
@@ -934,12 +973,12 @@ class ModConvActFn(Function):
             return (None,) * 15
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
             if ops.dot_fusable(x.shape[2], x.shape[3], x.dtype):
-                gx, gs = _modconv_dgrad_fused(gpre, w, spec, False, x, s, d, ws, ctx.in_port, ctx.needs_input_grad[2])
+                gx, gs = _modconv_dgrad_fused(gpre, w, spec, False, x, s, d, ws, in_port, ctx.needs_input_grad[2])
             else:
                 dxs = ops.conv_bwd_data(gpre, w, spec, tuple(x.shape[2:]), ws, in_scale=d)
                 gs, gx = ops.mul_reduce(dxs, x, scale=s, want_scaled=True)
-                if ctx.in_port is not None:
-                    gx = _mask_into_port(ctx.in_port, gx, x)
+                if port:
+                    gx = _mask_into_port(in_port, gx, x)
         if _need(ctx, 1):
             gw = ops.conv_wgrad(gpre, x, spec, O, I, ws, small_scale=d, big_scale=s, big_v=ctx.v)
         if ctx.needs_input_grad[3]:
@@ -947,7 +986,7 @@ class ModConvActFn(Function):
             gd = ops.act_inv_mul_reduce(gpre, y, residual, bias, slope, gain) / d
         gr = gra = None
         if has_res and ctx.needs_input_grad[4]:
-            if ctx.r_port is not None:
+            if _port_live(ctx.r_port):
                 gra = _deliver_residual(ctx.r_port, gpre, gb)
             else:
                 gr = gpre

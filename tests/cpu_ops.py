@@ -31,6 +31,8 @@ def _epilogue(z, cact, in_scale=None, out_scale=None, bias=None, residual=None, 
               out_f32=False):
     """fuse: gif_amd.ops.GradFuse — the gradient-producer fusions of gif_conv_epilogue ABI 2 (include/gif_hip.h)."""
     z = _pad_c(z, cact)
+    if fuse is not None and fuse.mask_src is None and fuse.dot_src is None:
+        raise ValueError("GradFuse: nothing to fuse")  # (gif_amd.ops._epilogue refuses such a launch)
     if fuse is not None and fuse.dot_src is not None:
         fuse.dot = (z * fuse.dot_src).sum(dim=(2, 3))  # contraction * dot_src, BEFORE out_scale
     if out_scale is not None:
