@@ -212,25 +212,25 @@ __device__ __host__ __forceinline__ int h2_exp_for(unsigned m_bits, int target) 
     return e > 126 ? 126 : (e < -126 ? -126 : e);
 }
 __device__ __forceinline__ float h2_pow2(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }  // -126 <= e <= 127
-// one pair of floats -> the packed {x1, x0} f16 dwords of the two terms (6 VALU: pk_mul, cvt_pk, 2 cvt, pk_fma / 2 sub, cvt_pk)
+// one pair of floats -> the packed {x1, x0} f16 dwords of the two terms, 5 VALU and no packed fp32 (v_pk_mul_f32 / v_pk_fma_f32 cost
+// ~32 cycles each beside MFMAs, and with a register-pair element select they returned wrong products while two waves shared a SIMD):
+// 2 v_mul_f32, v_cvt_pk_f16_f32, then v_fma_mixlo_f16 / v_fma_mixhi_f16 — an fp32 FMA with an f16 addend whose result is rounded into
+// one half of the destination — form lo = f16(x * 1.0 - hi): the subtraction is exact in fp32 (the rounding residual of an fp32 value
+// fits fp32), so this is subtract-then-convert, bit for bit (tools/probes/h2_split_mix.hip, tests/test_gpu_h2_split.py: all 2^32
+// patterns).  hipcc does not select the two instructions from C++; the empty asm statement keeps the two multiplies scalar.
 __device__ __forceinline__ void split_pair_h2(const float a0, const float a1, const float sc, unsigned& hi, unsigned& lo) {
-    const float x0 = a0 * sc, x1 = a1 * sc;
-    const f16x2_t h = __builtin_convertvector(f32x2_t{x0, x1}, f16x2_t);
-    const float r0 = x0 - (float)h[0], r1 = x1 - (float)h[1];  // exact: the rounding residual of an fp32 value fits fp32
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{r0, r1}, f16x2_t));
-}
-// the same with two scalar multiplies / subtracts (no v_pk_*_f32 with a register-pair element select)
-__device__ __forceinline__ void split_pair_h2_scalar(const float a0, const float a1, const float sc, unsigned& hi, unsigned& lo) {
     float x0 = a0 * sc;
     asm volatile("" : "+v"(x0));
     const float x1 = a1 * sc;
-    const f16x2_t h = __builtin_convertvector(f32x2_t{x0, x1}, f16x2_t);
-    float r0 = x0 - (float)h[0];
-    asm volatile("" : "+v"(r0));
-    const float r1 = x1 - (float)h[1];
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{r0, r1}, f16x2_t));
+    const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{x0, x1}, f16x2_t));
+    unsigned l = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+        : "=&v"(l) : "v"(x0), "v"(x1), "v"(h));
+#endif
+    hi = h;
+    lo = l;
 }
 // header of an f16x2 weight packing: int32 exponents of the RP rows, then RP int32 row flags ("a 16-element K group of this row
 // lies outside the window": launches that use the row take the bf16x3 fallback); the f16 planes follow.

@@ -820,7 +820,7 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
         // pipeline, per group: [LDS reads of the NEXT group's fp32 fragments] then the NPROD*MT*NT MFMAs of THIS group's
         // split operands with the split of the next group's fragments interleaved between them — the matrix pipe and the VALU
         // are separate, and the in-order wave only overlaps them when the instruction stream alternates (sched_barrier pins it).
-        // bf16x3: 6 products, 11 VALU per pair of floats.  f16x2 (H2): 3 products, 6 VALU per pair + the running row scale:
+        // bf16x3: 6 products, 11 VALU per pair of floats.  f16x2 (H2): 3 products, 5 VALU per pair + the running row scale:
         // per group and tile the maximum |a| of the lane's 8 floats (both lane halves exchange theirs: they feed the same row),
         // compared with the largest magnitude the row's current exponent can hold; in the rare case that a row outgrows it the
         // new exponent takes effect for the fragments split from here on and the row's accumulators are multiplied by the exact
@@ -909,18 +909,14 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             }
         };
         // piece k of the split of one group: one pair of floats -> one packed dword of each term (bf16x3: 11 VALU, +2 modulated;
-        // f16x2: 6)
+        // f16x2: 5)
         constexpr int NP = MT * 4;
         auto split_piece = [&](int slot, int k) __attribute__((always_inline)) {
             const int f = k / 4, e = k % 4;  // A tile, dword of the packed operand
             float a0 = ra[f][e / 2][(e % 2) * 2], a1 = ra[f][e / 2][(e % 2) * 2 + 1];
             if constexpr (H2) {
                 unsigned h, l;
-                // (two row tiles per lane: hipcc keeps the two scales in one register pair and selects the odd one with op_sel:[0,1] on
-                // v_pk_mul_f32 / v_pk_fma_f32 — that form returned wrong products in the weight-gradient kernel whenever two waves
-                // shared a SIMD, conv_wgrad.hip; the scalar form is two instructions longer)
-                if constexpr (MT > 1) gif::split_pair_h2_scalar(a0, a1, h_sc[f], h, l);
-                else gif::split_pair_h2(a0, a1, h_sc[f], h, l);
+                gif::split_pair_h2(a0, a1, h_sc[f], h, l);
                 sa[slot][0][f][e] = h; sa[slot][1][f][e] = l;
             } else {
                 if (SCALE) { a0 *= rs[f][e / 2][(e % 2) * 2]; a1 *= rs[f][e / 2][(e % 2) * 2 + 1]; }
@@ -1315,7 +1311,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_rows_thin_h2(const GatherParam
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         unsigned h, l;
-                        gif::split_pair_h2_scalar(ra[i][e / 2][(e % 2) * 2], ra[i][e / 2][(e % 2) * 2 + 1], h_sc[i], h, l);
+                        gif::split_pair_h2(ra[i][e / 2][(e % 2) * 2], ra[i][e / 2][(e % 2) * 2 + 1], h_sc[i], h, l);
                         sa[0][i][e] = h; sa[1][i][e] = l;
                     }
                 constexpr int TA3[3] = {1, 0, 0}, TB3[3] = {0, 1, 0};  // lo*hi, hi*lo, hi*hi

@@ -392,7 +392,7 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
     if constexpr (X3 && BKP == 32) {
         // ---- bf16x3 / f16x2, software-pipelined (two 16-pixel groups per stage; same schedule as conv_gather_mfma_glds' X3 path):
         //   DMA(stage+1) | MFMAs(g0) + read & split g1 | barrier | MFMAs(g1) + read & split g0 of stage+1
-        // The split of the NEXT group ((MT + NT) * 4 pieces: bf16x3 11 VALU each, +2 with per-sample scales; f16x2 6 VALU + the
+        // The split of the NEXT group ((MT + NT) * 4 pieces: bf16x3 11 VALU each, +2 with per-sample scales; f16x2 5 VALU + the
         // running exponents) sits piecewise between the MFMAs of the current one; sched_barrier(0) pins the interleave.
         constexpr bool H2 = X3 == 2;
         constexpr int NPL = H2 ? 2 : 3;
@@ -484,16 +484,16 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
             const int f = k / 4, e = k % 4;
             if constexpr (H2) {
                 unsigned h, l;
-                // scalar multiplies / subtracts: with several scales per lane hipcc keeps them in register pairs and picks the odd element
-                // with `op_sel:[0,1]` on v_pk_mul_f32 / v_pk_fma_f32 — the kernel then dropped products in lanes 16-31 / 48-63 of the
-                // second tile of each operand whenever two of its waves shared a SIMD (correct with one workgroup per CU, and with the
-                // scale as a constant: tools/probes/h2_wgrad_debug.py); cause on the hardware side not established
+                // (no packed fp32 in the split, common.h: with several scales per lane hipcc kept them in register pairs and picked the
+                // odd element with `op_sel:[0,1]` on v_pk_mul_f32 / v_pk_fma_f32 — the kernel then dropped products in lanes 16-31 /
+                // 48-63 of the second tile of each operand whenever two of its waves shared a SIMD (correct with one workgroup per CU, and
+                // with the scale as a constant: tools/probes/h2_wgrad_debug.py); cause on the hardware side not established)
                 const float scv = h_sc[f];
                 if (f < MT) {
-                    gif::split_pair_h2_scalar(ra[f][2 * e], ra[f][2 * e + 1], scv, h, l);
+                    gif::split_pair_h2(ra[f][2 * e], ra[f][2 * e + 1], scv, h, l);
                     sa[slot][0][f][e] = h; sa[slot][1][f][e] = l;
                 } else {
-                    gif::split_pair_h2_scalar(rb[f - MT][2 * e], rb[f - MT][2 * e + 1], scv, h, l);
+                    gif::split_pair_h2(rb[f - MT][2 * e], rb[f - MT][2 * e + 1], scv, h, l);
                     sb[slot][0][f - MT][e] = h; sb[slot][1][f - MT][e] = l;
                 }
             } else {
