@@ -76,6 +76,9 @@ PROTOTYPES = {
                                      P, P, c_int, c_int, c_int, P]),
     "gif_texture_map_f32": (c_int, [P] * 9 + [c_int] * 6 + [P]),
     "gif_texture_map_bwd_f32": (c_int, [P] * 8 + [c_int] * 6 + [P]),
+    "gif_shade_sh_f32": (c_int, [P] * 6 + [c_int] * 5 + [c_float, c_float, P]),
+    "gif_shade_sh_bwd_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "gif_shade_sh_bwd_f32": (c_int, [P] * 10 + [c_int] * 5 + [c_float, c_float, P, P]),
     "gif_conv_epilogue_ws_floats": (c_i64, [c_i64, c_int]),
     "gif_conv2d_pack_dims": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "gif_pack_weight_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_float, P]),

@@ -7,8 +7,8 @@ Mirrors the pieces of the reference that exist in-tree:
   [-1,1] scaling and channel order       plots/generate_random_samples.py:22-30, :188-189  (cat(texture, normal))
 The FLAME layer lives in the reference's absent `photometric_optimization` submodule; its algorithm is public and is built
 here as gif_amd.flame.FlameLayer (HIP forward and backward) — only the licensed model file stays outside.  The
-spherical-harmonics texture shading of that submodule is out of scope (parity unpinned): the per-vertex "texture" attribute
-is therefore an INPUT here.
+per-vertex "texture" attribute is an INPUT here; the condition GIF actually uses — the FLAME albedo texture lit by spherical
+harmonics — is gif_amd.shading.render_shaded_condition, built on the same rasteriser passes.
 Kernels: gif_vertex_normals_f32 (gather, deterministic) and gif_rasterize_colors_f32, both behind the C ABI.
 Backward (differentiable condition rendering): gif_vertex_normals_bwd_f32, gif_rasterize_colors_bwd_f32 and
 gif_face_gather_bwd_f32, all deterministic (no float atomics).
@@ -115,23 +115,58 @@ def batch_orth_proj(X, camera):
     return camera[:, :, 0:1] * X_trans
 
 
+def _rasterize_colors(vertices_ndc, faces, face_colors_of, h, w):
+    """The forward both attribute rasterisers share: (fv, fc, tri, image [B,3,h,w], mask [B,1,h,w]); `face_colors_of(faces_b)`
+    gives the per-face-corner attributes [B,F,3,3]."""
+    B = vertices_ndc.shape[0]
+    faces_b = faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
+    v = sr.to_image_space(vertices_ndc.float(), h, w)
+    fv = sr.face_vertices(v, faces_b)
+    fc = face_colors_of(faces_b)
+    depth, tri, img = sr.new_buffers(B, h, w, vertices_ndc.device)
+    sr.standard_rasterize_colors(fv, fc, depth, tri, img, h, w)
+    return fv, fc, tri, img.permute(0, 3, 1, 2).contiguous(), (tri >= 0)[:, None]
+
+
+def _rasterize_colors_bwd(fv, fc, tri, gimg, faces, V, vdtype, h, w, need_v, need_c, what):
+    """d image -> (d vertices_ndc [B,V,3] in `vdtype` or None, d face colours [B,F,3,3] or None): gif_rasterize_colors_bwd_f32,
+    then for the vertices the face gather's transpose and the NDC -> pixel scaling."""
+    B, F = fv.shape[:2]
+    if faces.ndimension() == 3 and B > 1 and faces.stride(0) != 0 and not torch.equal(faces, faces[:1].expand_as(faces)):
+        raise _lib.GifHipError(f"{what} backward needs one face topology for the whole batch")
+    dev = fv.device
+    lib = _lib.load()
+    g = gimg.float().permute(0, 2, 3, 1).contiguous()  # [B,H,W,3]: the forward's image buffer layout
+    gfv = torch.empty_like(fv) if need_v else None
+    gfc = torch.empty_like(fc) if need_c else None
+    ws = torch.empty((max(lib.gif_rasterize_colors_bwd_workspace_bytes(B, F, h, w) // 4, 1),), device=dev,
+                     dtype=torch.float32)
+    gv = None
+    with torch.cuda.device(dev):
+        _lib.check(lib.gif_rasterize_colors_bwd_f32(fv.data_ptr(), fc.data_ptr(), tri.data_ptr(), g.data_ptr(),
+                                                    gfv.data_ptr() if need_v else None,
+                                                    gfc.data_ptr() if need_c else None, B, F, h, w, ws.data_ptr(),
+                                                    torch.cuda.current_stream().cuda_stream), "rasterize_colors_bwd")
+        if need_v:
+            _, off, ent = _topology(faces, V, dev)
+            gv = _face_gather_bwd(gfv, off, ent, V)
+            # to_image_space: x * w/2 + w/2, y * h/2 + h/2; z only orders the faces (no gradient)
+            gv *= torch.tensor([w / 2, h / 2, 0.0], device=dev, dtype=torch.float32)
+            gv = gv.to(vdtype)
+    return gv, gfc
+
+
 class _RasterizeAttributesFn(Function):
     @staticmethod
     def forward(ctx, vertices_ndc, attributes, faces, h, w):
-        B = vertices_ndc.shape[0]
-        faces_b = faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
-        v = sr.to_image_space(vertices_ndc.float(), h, w)
-        fv = sr.face_vertices(v, faces_b)
-        fc = sr.face_vertices(attributes.float().contiguous(), faces_b)
-        depth, tri, img = sr.new_buffers(B, h, w, vertices_ndc.device)
-        sr.standard_rasterize_colors(fv, fc, depth, tri, img, h, w)
-        mask = (tri >= 0)[:, None]
+        fv, fc, tri, img, mask = _rasterize_colors(
+            vertices_ndc, faces, lambda faces_b: sr.face_vertices(attributes.float().contiguous(), faces_b), h, w)
         ctx.mark_non_differentiable(mask)
         ctx.save_for_backward(fv, fc, tri)
         ctx.faces, ctx.hw = faces, (h, w)
         ctx.dtypes = (vertices_ndc.dtype, attributes.dtype)
         ctx.V = (vertices_ndc.shape[1], attributes.shape[1])
-        return img.permute(0, 3, 1, 2).contiguous(), mask
+        return img, mask
 
     @staticmethod
     @once_differentiable  # raw kernel launch: a double backward must fail loudly, not return a history-free gradient
@@ -139,30 +174,12 @@ class _RasterizeAttributesFn(Function):
         fv, fc, tri = ctx.saved_tensors
         faces, (h, w) = ctx.faces, ctx.hw
         need_v, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        B, F = fv.shape[:2]
-        if faces.ndimension() == 3 and B > 1 and faces.stride(0) != 0 and not torch.equal(faces, faces[:1].expand_as(faces)):
-            raise _lib.GifHipError("rasterize_attributes backward needs one face topology for the whole batch")
-        dev = fv.device
-        lib = _lib.load()
-        g = gimg.float().permute(0, 2, 3, 1).contiguous()  # [B,H,W,3]: the forward's image buffer layout
-        gfv = torch.empty_like(fv) if need_v else None
-        gfc = torch.empty_like(fc) if need_a else None
-        ws = torch.empty((max(lib.gif_rasterize_colors_bwd_workspace_bytes(B, F, h, w) // 4, 1),), device=dev,
-                         dtype=torch.float32)
-        gv = ga = None
-        with torch.cuda.device(dev):
-            _lib.check(lib.gif_rasterize_colors_bwd_f32(fv.data_ptr(), fc.data_ptr(), tri.data_ptr(), g.data_ptr(),
-                                                        gfv.data_ptr() if need_v else None,
-                                                        gfc.data_ptr() if need_a else None, B, F, h, w, ws.data_ptr(),
-                                                        torch.cuda.current_stream().cuda_stream), "rasterize_colors_bwd")
-            if need_v:
-                _, off, ent = _topology(faces, ctx.V[0], dev)
-                gv = _face_gather_bwd(gfv, off, ent, ctx.V[0])
-                # to_image_space: x * w/2 + w/2, y * h/2 + h/2; z only orders the faces (no gradient)
-                gv *= torch.tensor([w / 2, h / 2, 0.0], device=dev, dtype=torch.float32)
-                gv = gv.to(ctx.dtypes[0])
-            if need_a:
-                _, off, ent = _topology(faces, ctx.V[1], dev)
+        gv, gfc = _rasterize_colors_bwd(fv, fc, tri, gimg, faces, ctx.V[0], ctx.dtypes[0], h, w, need_v, need_a,
+                                        "rasterize_attributes")
+        ga = None
+        if need_a:
+            with torch.cuda.device(fv.device):
+                _, off, ent = _topology(faces, ctx.V[1], fv.device)
                 ga = _face_gather_bwd(gfc, off, ent, ctx.V[1]).to(ctx.dtypes[1])
         return gv, ga, None, None, None
 
@@ -204,8 +221,9 @@ class FlameConditionRenderer:
     OverLayViz.get_rendered_mesh + the [-1,1] scaling play in InterpolatedTextureLoss.get_image_and_textures
     (loss_functions/losses.py:184-215).  `flame` is the FLAME layer: gif_amd.flame.FlameLayer over a converted model file or
     over flame.synthetic_flame_model (differentiable with respect to shape, expression and pose), any callable with its
-    signature, or gif_amd.data.SyntheticFlame, the benchmark's fixed stand-in.  `vertex_texture` [V,3] in [0,1] replaces the
-    SH-lit albedo render (out of scope)."""
+    signature, or gif_amd.data.SyntheticFlame, the benchmark's fixed stand-in.  `vertex_texture` [V,3] in [0,1] is a fixed per-vertex
+    colour in place of the SH-lit albedo render; gif_amd.shading.ShadedFlameConditionRenderer renders that one from columns
+    159:236 of the labels."""
 
     def __init__(self, flame, faces, vertex_texture, h=256, w=256, straight_through=False):
         self.flame, self.faces, self.vertex_texture, self.h, self.w = flame, faces, vertex_texture, h, w

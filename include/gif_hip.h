@@ -238,6 +238,39 @@ int gif_texture_map_bwd_f32(const float* gtex, const float* verts, const float* 
                             const int32_t* texel_map, const int32_t* texel_faces, const float* texel_bc, float* gimg,
                             int B, int C, int H, int W, int V, int T, gif_stream_t stream);
 
+/* Shaded condition render: deferred shading in image space — the albedo texture sampled at a rasterised UV
+ * coordinate, lit by second-order spherical-harmonics irradiance (Ramamoorthi & Hanrahan 2001; the definition DECA's light codes
+ * are written for) of a rasterised normal.  The reference keeps its renderer in an absent submodule, so there is no line to cite.
+ * All tensors fp32, contiguous, planar NCHW (what the attribute rasteriser's Python wrapper returns):
+ *   uv [B,3,H,W] = (grid x, grid y, unused); nrm [B,3,H,W]; mask [B,1,H,W] u8, 0 = background; albedo [Ba,3,T,T], Ba == 1 (one
+ *   texture for the whole batch) or Ba == B; sh [B,9,3]; out [B,3,H,W].
+ * gif_shade_sh_f32, per pixel with mask != 0 (out = 0 elsewhere):
+ *   n = nrm_mul * nrm + nrm_add (not re-normalised; (2, -1) takes the [0,1]-mapped normal image of the condition as it is)
+ *   a_c = bilinear sample of albedo[b or 0, c] at grid (uv_x, uv_y) with the semantics of grid_sample(bilinear, zeros,
+ *         align_corners=False): texel position ((g + 1) T - 1) / 2, taps outside [0, T-1] contribute 0, a NaN coordinate is outside
+ *   shading_c = sum_{i<9} k_i basis_i(n) sh[b,i,c],  basis = (1, x, y, z, xy, xz, yz, x^2 - y^2, 3 z^2 - 1),
+ *   k = A_l Y_lm with A = (1, 2pi/3, pi/4) — DECA's table, which leaves band 0's factor pi to the light code: 1/sqrt(4pi); (2pi/3) sqrt(3/(4pi)) x3; (pi/4) 3 sqrt(5/(12pi)) x3;
+ *       (pi/4)(3/2) sqrt(5/(12pi)); (pi/4)(1/2) sqrt(5/(4pi))
+ *   out_c = a_c * shading_c
+ * gif_shade_sh_bwd_f32: g_out [B,3,H,W] = dL/d out -> (background pixels contribute nothing)
+ *   g_uv [B,3,H,W]: the bilinear derivative with respect to grid x, y (factor T/2; a tap outside counts as a 0 texel);
+ *                   channel 2 is written 0, so the tensor feeds gif_rasterize_colors_bwd_f32 as it stands
+ *   g_nrm [B,3,H,W]: includes nrm_mul        g_sh [B,9,3]        g_albedo [Ba,3,T,T]
+ * Each output may be null: it is not computed, and work only it needs is not launched.  g_uv, g_nrm and g_sh are deterministic:
+ * g_sh is 27 sums over H*W per sample — one partial row per workgroup in `workspace` (gif_shade_sh_bwd_workspace_bytes(B, H, W)
+ * bytes, 4-byte aligned, no initialisation needed), then a fixed-order sum; no float atomics, run-to-run identical bits.
+ * g_albedo is NOT: it is zeroed inside and accumulated with fp32 atomicAdd (four taps x three channels per pixel; over the whole
+ * batch when Ba == 1), so its last bits depend on arrival order — with gif_texture_map_bwd_f32 one of the two non-deterministic
+ * backwards of the library, and like it never on the training step's or inference's path (labels are data there).
+ * B, H, W, T < 0, Ba outside {1, B}, B*3*H*W >= 2^31, a null required pointer, or (backward) T == 0 with g_albedo: GIF_EINVAL.
+ * B*H*W == 0: no-op.  T == 0 (forward): every tap is outside, out = 0. */
+int gif_shade_sh_f32(const float* uv, const float* nrm, const uint8_t* mask, const float* albedo, const float* sh, float* out,
+                     int B, int Ba, int H, int W, int T, float nrm_mul, float nrm_add, gif_stream_t stream);
+int64_t gif_shade_sh_bwd_workspace_bytes(int B, int H, int W);
+int gif_shade_sh_bwd_f32(const float* uv, const float* nrm, const uint8_t* mask, const float* albedo, const float* sh,
+                         const float* g_out, float* g_uv, float* g_nrm, float* g_albedo, float* g_sh, int B, int Ba, int H,
+                         int W, int T, float nrm_mul, float nrm_add, void* workspace, gif_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Convolution family (fp32 MFMA implicit GEMM) — replaces the F.conv2d / F.conv_transpose2d calls of
  *   ModulatedConv2d.forward   stylegan2_common_layers.py:307-349 (groups=batch trick -> in/out scales)
