@@ -8,8 +8,14 @@ FlameTextureSpace.forward uses (model/stg2_generator.py:362-364); DESIGN.md §3l
 * FlameModel            — the six constant arrays of a model; .npz in and out (what a licensed model file is converted into).
 * synthetic_flame_model — a model with FLAME's structure over any template mesh (no assets needed to build, test or measure).
 * FlameLayer            — nn.Module, `FlameLayer(model)(shape_params, expression_params, pose_params) -> (vertices, None, None)`;
-                          drops into render.FlameConditionRenderer(flame=...).
-Kernels (csrc/flame.hip): gif_flame_joints_f32, gif_flame_skin_f32, gif_flame_skin_bwd_f32.  No CPU fallback.
+                          drops into render.FlameConditionRenderer(flame=...).  With `landmarks=` an embedding the outputs are
+                          (vertices, landmarks2d, landmarks3d), the reference layer's three.
+* FlameLandmarkEmbedding — the landmark tables in vertex-id form (.npz in and out; from_face_embedding converts the layout of
+                          `landmark_embedding.npy`); synthetic_landmark_embedding builds one over any face list.
+* FlameLandmarkLayer    — (landmarks2d, landmarks3d) alone: the layer restricted to the few hundred vertices the tables name.
+* project_landmarks     — orthographic projection with y and z flipped, as the reference draws landmarks.
+Kernels: gif_flame_joints_f32, gif_flame_skin_f32, gif_flame_skin_bwd_f32 (csrc/flame.hip), gif_flame_landmarks_f32,
+gif_flame_landmarks_bwd_f32 (csrc/flame_landmarks.hip).  No CPU fallback.
 """
 import ctypes
 
@@ -113,6 +119,130 @@ def synthetic_flame_model(template, n_shape=100, n_exp=50, seed=0, amplitude=2e-
     return FlameModel(t, shapedirs, posedirs, J_regressor, w / w.sum(1, keepdims=True), parents, n_shape=n_shape)
 
 
+class FlameLandmarkEmbedding:
+    """Landmark tables in vertex-id form.  A landmark is sum_i bary[i] * vertex[vid[i]]:
+      static_vid [Ls,3] int, static_bary [Ls,3]        the static landmarks of `landmarks2d` (FLAME: Ls = 51);
+      dynamic_vid [R,Ld,3] int, dynamic_bary [R,Ld,3]  the contour landmarks, R = 2M + 1 rows, one chosen per sample from the yaw of
+                                                      joint `yaw_joint` (FLAME: R = 79, Ld = 17, joint 1 = the neck);
+      full_vid [Lf,3] int, full_bary [Lf,3]            the static "full" set, `landmarks3d` (FLAME: Lf = 68).
+    Shapes, R odd, ids >= 0 and finite weights are checked here; ids < V by check_vertices(V), which the layers call."""
+
+    KEYS = ("static_vid", "static_bary", "dynamic_vid", "dynamic_bary", "full_vid", "full_bary", "yaw_joint")
+
+    def __init__(self, static_vid, static_bary, dynamic_vid, dynamic_bary, full_vid, full_bary, yaw_joint=1):
+        for name, vid, bary, nd in (("static", static_vid, static_bary, 2), ("dynamic", dynamic_vid, dynamic_bary, 3),
+                                    ("full", full_vid, full_bary, 2)):
+            vid, bary = np.asarray(vid), np.asarray(bary, np.float64)
+            want = "[R,Ld,3]" if nd == 3 else "[L,3]"
+            if vid.ndim != nd or vid.shape[-1] != 3:
+                raise ValueError(f"{name}_vid must be {want}, got {list(vid.shape)}")
+            if bary.shape != vid.shape:
+                raise ValueError(f"{name}_bary must have {name}_vid's shape {list(vid.shape)}, got {list(bary.shape)}")
+            if vid.size and not np.issubdtype(vid.dtype, np.integer):
+                raise ValueError(f"{name}_vid must hold integers, got {vid.dtype}")
+            vid = vid.astype(np.int64)
+            if vid.size and vid.min() < 0:
+                raise ValueError(f"{name}_vid holds the negative vertex id {int(vid.min())}")
+            if not np.isfinite(bary).all():
+                raise ValueError(f"{name}_bary holds non-finite weights")
+            setattr(self, name + "_vid", vid)
+            setattr(self, name + "_bary", bary)
+        R, Ld = self.dynamic_vid.shape[:2]
+        if Ld > 0 and R % 2 == 0:
+            raise ValueError(f"dynamic tables have R = {R} rows: R must be odd (2M + 1, rows for yaw 0..M, then -1..-M)")
+        self.yaw_joint = int(yaw_joint)
+        if not 0 <= self.yaw_joint < MAX_JOINTS:
+            raise ValueError(f"yaw_joint = {yaw_joint} outside 0..{MAX_JOINTS - 1}")
+
+    @classmethod
+    def from_face_embedding(cls, faces, static_faces_idx, static_bary, dynamic_faces_idx, dynamic_bary, full_faces_idx, full_bary,
+                            yaw_joint=1):
+        """From face indices into `faces` [F,3], the layout of the FLAME distribution's `landmark_embedding.npy`.  That file is a
+        pickled dict (this library loads no pickle; the caller does, `np.load(path, allow_pickle=True, encoding="latin1")[()]`):
+          static_lmk_faces_idx [51], static_lmk_bary_coords [51,3]            -> static_faces_idx, static_bary
+          dynamic_lmk_faces_idx [79,17], dynamic_lmk_bary_coords [79,17,3]    -> dynamic_faces_idx, dynamic_bary
+          full_lmk_faces_idx [1,68], full_lmk_bary_coords [1,68,3]            -> full_faces_idx, full_bary (a leading 1 is dropped)
+        and `faces` is the model's face list."""
+        faces = np.asarray(faces)
+        if faces.ndim != 2 or faces.shape[1] != 3:
+            raise ValueError(f"faces must be [F,3], got {list(faces.shape)}")
+        full_faces_idx, full_bary = np.asarray(full_faces_idx), np.asarray(full_bary)
+        if full_faces_idx.ndim == 2 and full_faces_idx.shape[0] == 1:
+            full_faces_idx, full_bary = full_faces_idx[0], full_bary.reshape(full_bary.shape[-2:])
+        vids = []
+        for name, idx in (("static", static_faces_idx), ("dynamic", dynamic_faces_idx), ("full", full_faces_idx)):
+            idx = np.asarray(idx)
+            if idx.size and not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError(f"{name}_faces_idx must hold integers, got {idx.dtype}")
+            idx = idx.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= faces.shape[0]):
+                raise ValueError(f"{name}_faces_idx outside 0..{faces.shape[0] - 1}")
+            vids.append(faces[idx].reshape(idx.shape + (3,)))
+        return cls(vids[0], static_bary, vids[1], dynamic_bary, vids[2], full_bary, yaw_joint)
+
+    def check_vertices(self, V):
+        """Raise unless every vertex id is in 0..V-1."""
+        for name in ("static", "dynamic", "full"):
+            vid = getattr(self, name + "_vid")
+            if vid.size and vid.max() >= V:
+                raise ValueError(f"{name}_vid holds vertex id {int(vid.max())}, outside 0..{V - 1}")
+
+    def vertex_ids(self):
+        """Sorted unique vertex ids over all tables."""
+        return np.unique(np.concatenate([self.static_vid.reshape(-1), self.dynamic_vid.reshape(-1), self.full_vid.reshape(-1)]))
+
+    def remapped(self, ids):
+        """The same tables over the compact vertex list `ids` (sorted, unique, a superset of vertex_ids()): id -> its position."""
+        ids = np.asarray(ids, np.int64)
+        pos = lambda vid: np.searchsorted(ids, vid).reshape(vid.shape)
+        for vid in (self.static_vid, self.dynamic_vid, self.full_vid):
+            if vid.size and not np.array_equal(ids[np.minimum(pos(vid), len(ids) - 1)], vid):
+                raise ValueError("remapped: a vertex id of the tables is missing from ids")
+        return FlameLandmarkEmbedding(pos(self.static_vid), self.static_bary, pos(self.dynamic_vid), self.dynamic_bary,
+                                      pos(self.full_vid), self.full_bary, self.yaw_joint)
+
+    def save_npz(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, **{k: np.asarray(getattr(self, k)) for k in self.KEYS})
+
+    @classmethod
+    def from_npz(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            missing = [k for k in cls.KEYS if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: missing keys {missing}")
+            return cls(*[z[k] for k in cls.KEYS[:-1]], yaw_joint=int(z["yaw_joint"]))
+
+
+def synthetic_landmark_embedding(faces, n_dynamic=17, n_static=51, n_full=68, n_rows=79, seed=0):
+    """An embedding with FLAME's structure over `faces` [F,3]: positive barycentric weights that sum to 1, and dynamic faces drawn
+    from one sequence, face[r, c] = seq[(r + c) // 2], so neighbouring rows share faces and neighbouring columns of a row sit on
+    one face (the collisions of a profile view).  Deterministic per seed.  NOT a face's landmarks: their structure."""
+    faces = np.asarray(faces, np.int64)
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise ValueError(f"faces must be [F,3] with F >= 1, got {list(faces.shape)}")
+    rng = np.random.RandomState(seed)
+    F = faces.shape[0]
+
+    def bary(*shape):
+        w = 0.1 + rng.rand(*shape, 3)
+        return w / w.sum(-1, keepdims=True)
+
+    seq = rng.randint(0, F, (n_rows + n_dynamic + 1) // 2 + 1)
+    dyn_idx = seq[(np.arange(n_rows)[:, None] + np.arange(n_dynamic)[None, :]) // 2]
+    st_idx, full_idx = rng.randint(0, F, n_static), rng.randint(0, F, n_full)
+    return FlameLandmarkEmbedding.from_face_embedding(faces, st_idx, bary(n_static), dyn_idx, bary(n_rows, n_dynamic), full_idx,
+                                                      bary(n_full))
+
+
+def project_landmarks(lmk, cam):
+    """Landmarks [B,L,3] under the orthographic camera [B,3] = (s, tx, ty), components 1 and 2 negated: render.batch_orth_proj
+    and the flip the reference applies before it draws them (plots/voca/generate_voca_gt.py:68-69).  Plain torch."""
+    from .render import batch_orth_proj
+    p = batch_orth_proj(lmk, cam)
+    return torch.cat([p[:, :, :1], -p[:, :, 1:]], 2)
+
+
 def joint_basis(model, n_shape, n_exp):
     """(tmpl [V,3], sd [V,3,K], J0 [J,3], Jdirs [K,3J]): the layer's fp32 template and selected blend-shape columns, and the
     joints as a linear function of betas — joints = J0 + betas . Jdirs with J0 = J_regressor . v_template and Jdirs =
@@ -177,17 +307,76 @@ class _FlameSkinFn(Function):
         return g_coef, g_A, None, None, None
 
 
+def _launch_landmarks_bwd(g_lmk, row, tables, g_verts, B, V, R, Ld, Ls):
+    """The one place gif_flame_landmarks_bwd_f32 is launched from (on g_verts' device and its current stream)."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(g_verts.device):
+        _lib.check(_lib.load().gif_flame_landmarks_bwd_f32(g_lmk.data_ptr(), ptr(row), *[ptr(t) for t in tables], g_verts.data_ptr(),
+                                                           B, V, R, Ld, Ls, torch.cuda.current_stream().cuda_stream),
+                   "flame_landmarks_bwd")
+
+
+class _FlameLandmarksFn(Function):
+    """lmk [B,Ld+Ls,3] = cat(dynamic[row(A[:, yaw_joint])], static) landmarks of verts, on gif_flame_landmarks_f32 /
+    gif_flame_landmarks_bwd_f32.  tables = (dyn_vid [R,Ld,3] int32, dyn_bary, st_vid [Ls,3] int32, st_bary); an empty table is
+    None.  The gradient goes to verts alone: the row choice is piecewise constant in A."""
+
+    @staticmethod
+    def forward(ctx, verts, A, yaw_joint, R, Ld, Ls, dyn_vid, dyn_bary, st_vid, st_bary):
+        if not (verts.is_cuda and A.is_cuda):
+            raise _lib.GifHipError("flame landmarks need device tensors (no CPU fallback)")
+        B, V, _ = verts.shape
+        J = A.shape[1]
+        verts, A = verts.contiguous().float(), A.contiguous().float()
+        tables = (dyn_vid, dyn_bary, st_vid, st_bary)
+        lmk = torch.empty((B, Ld + Ls, 3), device=verts.device, dtype=torch.float32)
+        row = torch.empty((B,), device=verts.device, dtype=torch.int32)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(verts.device):  # launch on the operands' device and its current stream
+            _lib.check(_lib.load().gif_flame_landmarks_f32(verts.data_ptr(), A.data_ptr(), *[ptr(t) for t in tables], lmk.data_ptr(),
+                                                           row.data_ptr(), B, V, J, yaw_joint, R, Ld, Ls,
+                                                           torch.cuda.current_stream().cuda_stream), "flame_landmarks")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(row, *[t for t in tables if t is not None])
+            ctx.present = [t is not None for t in tables]
+        ctx.dims = (B, V, R, Ld, Ls)
+        ctx.mark_non_differentiable(row)
+        return lmk, row
+
+    @staticmethod
+    @once_differentiable  # raw kernel launch: a double backward must fail loudly
+    def backward(ctx, g_lmk, _g_row):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 10  # nothing to launch: A receives no gradient
+        row, *rest = ctx.saved_tensors
+        rest = iter(rest)
+        tables = [next(rest) if have else None for have in ctx.present]
+        B, V, R, Ld, Ls = ctx.dims
+        g = g_lmk.contiguous().float()
+        g_verts = torch.empty((B, V, 3), device=g.device, dtype=torch.float32)
+        _launch_landmarks_bwd(g, row, tables, g_verts, B, V, R, Ld, Ls)
+        return (g_verts,) + (None,) * 9
+
+
 class FlameLayer(nn.Module):
     """FLAME layer over a FlameModel: the first `n_shape` shape columns and the first `n_exp` expression columns of its
     shapedirs.  forward(shape_params [B,n_shape], expression_params [B,n_exp], pose_params [B,6] = (global, jaw) axis-angle,
-    neck_pose [B,3], eye_pose [B,6]) -> (vertices [B,V,3], None, None); missing arguments are zeros; the landmark outputs are
-    not computed.  A model with J != 5 joints takes the first 3 J entries of cat(global, neck, jaw, eyes) (zeros past the fifth).
+    neck_pose [B,3], eye_pose [B,6]) -> (vertices [B,V,3], landmarks2d, landmarks3d); missing arguments are zeros.  A model with
+    J != 5 joints takes the first 3 J entries of cat(global, neck, jaw, eyes) (zeros past the fifth).
+
+    `landmarks`: a FlameLandmarkEmbedding over the layer's vertices -> landmarks2d [B,Ld+Ls,3] = cat(the dynamic contour row chosen
+    from the yaw of joint `yaw_joint`, the static landmarks) and landmarks3d [B,Lf,3] (the static "full" set): one more launch
+    (gif_flame_landmarks_f32) on the vertices and the chain's transforms A, both already on the device; differentiable through
+    the vertices.  None (the default): both outputs are None and nothing else changes.
+    `vertex_ids`: keep only these rows of the model's vertices (template rows, the three dirs columns per vertex, lbs_weights
+    rows); the joints still come from the full model (J0, Jdirs), so the kept vertices move exactly as they do in the full layer.
+    The landmark tables then index the kept list.
 
     No input requires a gradient: two launches (gif_flame_joints_f32, gif_flame_skin_f32).  Otherwise the joints, the rotations
     and the chain run as torch ops on [B,J,.] tensors — the same J0 + Jdirs . betas form, so both paths compute one function —
     and autograd carries the skin kernels' g_coef / g_A back through them.  The constants receive no gradient."""
 
-    def __init__(self, model, n_shape=100, n_exp=50):
+    def __init__(self, model, n_shape=100, n_exp=50, landmarks=None, vertex_ids=None):
         super().__init__()
         if not (0 <= n_shape <= model.n_shape and 0 <= n_exp <= model.n_exp):
             raise ValueError(f"model has {model.n_shape} shape and {model.n_exp} expression columns; asked for {n_shape}, {n_exp}")
@@ -196,11 +385,35 @@ class FlameLayer(nn.Module):
         V, J = model.lbs_weights.shape
         tmpl, sd, J0, Jdirs = joint_basis(model, n_shape, n_exp)  # (computed in fp64, rounded once)
         dirs = np.concatenate([sd.reshape(3 * V, -1).T, f32(model.posedirs)], 0)  # [KP,3V], k-major
+        lbs_w = f32(model.lbs_weights)
+        if vertex_ids is not None:
+            ids = np.asarray(vertex_ids)
+            if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+                raise ValueError(f"vertex_ids must be a 1-D integer array, got {ids.dtype} {list(ids.shape)}")
+            ids = ids.astype(np.int64)
+            if ids.size and (ids.min() < 0 or ids.max() >= V):
+                raise ValueError(f"vertex_ids outside 0..{V - 1}")
+            tmpl, lbs_w = tmpl[ids], lbs_w[ids]
+            dirs = dirs.reshape(-1, V, 3)[:, ids].reshape(dirs.shape[0], 3 * len(ids))
+            V = len(ids)
         self.parents = tuple(int(p) for p in model.parents)
         self._parents_c = (ctypes.c_int32 * J)(*self.parents)
-        for name, a in (("v_template", tmpl.reshape(-1)), ("dirs", dirs), ("lbs_weights", f32(model.lbs_weights)),
+        for name, a in (("v_template", tmpl.reshape(-1)), ("dirs", dirs), ("lbs_weights", lbs_w),
                         ("J0", f32(J0).reshape(-1)), ("Jdirs", f32(Jdirs))):
             self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(a)))
+        self._lmk = None
+        if landmarks is not None:
+            landmarks.check_vertices(V)
+            if not landmarks.yaw_joint < J:
+                raise ValueError(f"landmarks.yaw_joint = {landmarks.yaw_joint} outside 0..{J - 1}")
+            # one static table: the Ls static landmarks of landmarks2d, then the Lf of landmarks3d — one launch yields both
+            st_vid = np.concatenate([landmarks.static_vid, landmarks.full_vid], 0)
+            st_bary = np.concatenate([landmarks.static_bary, landmarks.full_bary], 0)
+            R, Ld = landmarks.dynamic_vid.shape[:2]
+            self._lmk = (landmarks.yaw_joint, R, Ld, landmarks.static_vid.shape[0], landmarks.full_vid.shape[0])
+            for name, a, dt in (("lmk_dyn_vid", landmarks.dynamic_vid, np.int32), ("lmk_dyn_bary", landmarks.dynamic_bary, np.float32),
+                                ("lmk_st_vid", st_vid, np.int32), ("lmk_st_bary", st_bary, np.float32)):
+                self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(np.asarray(a, dt))))
 
     @property
     def n_vertices(self):
@@ -226,8 +439,10 @@ class FlameLayer(nn.Module):
             (shape_params, self.n_shape, "shape_params"), (expression_params, self.n_exp, "expression_params"),
             (pose_params, 6, "pose_params"), (neck_pose, 3, "neck_pose"), (eye_pose, 6, "eye_pose"))]
         if torch.is_grad_enabled() and any(t.requires_grad for t in given):
-            return self._forward_grad(B, *ins), None, None
-        return self._forward_nograd(B, ins), None, None
+            verts, A = self._forward_grad(B, *ins)
+        else:
+            verts, A = self._forward_nograd(B, ins)
+        return (verts,) + self._landmarks(verts, A)
 
     def _forward_nograd(self, B, ins):
         dev = self.dirs.device
@@ -255,7 +470,7 @@ class FlameLayer(nn.Module):
             _lib.check(lib.gif_flame_skin_f32(self.v_template.data_ptr(), self.dirs.data_ptr(), self.lbs_weights.data_ptr(),
                                               coef.data_ptr(), A.data_ptr(), verts.data_ptr(), None, B, V, KP, J, stream),
                        "flame_skin")
-        return verts
+        return verts, A
 
     def _forward_grad(self, B, shape, exp, pose, neck, eye):
         dev = self.dirs.device
@@ -276,4 +491,30 @@ class FlameLayer(nn.Module):
             Gt.append((GR[p] @ (joints[:, j] - joints[:, p])[:, :, None])[:, :, 0] + Gt[p])
         GR, Gt = torch.stack(GR, 1), torch.stack(Gt, 1)
         A = torch.cat([GR, (Gt - (GR @ joints[..., None])[..., 0])[..., None]], 3).reshape(B, J, 12)
-        return _FlameSkinFn.apply(torch.cat([betas, pose_feature], 1), A, self.v_template, self.dirs, self.lbs_weights)
+        return _FlameSkinFn.apply(torch.cat([betas, pose_feature], 1), A, self.v_template, self.dirs, self.lbs_weights), A
+
+    def _landmarks(self, verts, A):
+        """(landmarks2d, landmarks3d) of the layer's vertices: one launch over the concatenated static table, split into views."""
+        if self._lmk is None:
+            return None, None
+        yaw_joint, R, Ld, Ls, Lf = self._lmk
+        if Ld + Ls + Lf == 0:
+            return verts.new_empty((verts.shape[0], 0, 3)), verts.new_empty((verts.shape[0], 0, 3))
+        some = lambda t: t if t.numel() else None
+        lmk, _ = _FlameLandmarksFn.apply(verts, A, yaw_joint, R, Ld, Ls + Lf, some(self.lmk_dyn_vid), some(self.lmk_dyn_bary),
+                                         some(self.lmk_st_vid), some(self.lmk_st_bary))
+        return lmk[:, :Ld + Ls], lmk[:, Ld + Ls:]
+
+
+class FlameLandmarkLayer(FlameLayer):
+    """(landmarks2d, landmarks3d) alone: a FlameLayer over embedding.vertex_ids() — the few hundred vertices the tables name — with
+    the tables remapped to that compact list, so a landmark fit skins those vertices instead of all V, forward and backward.  Same
+    arguments as FlameLayer.forward; the landmarks are those of FlameLayer(model, landmarks=embedding)."""
+
+    def __init__(self, model, embedding, n_shape=100, n_exp=50):
+        embedding.check_vertices(model.lbs_weights.shape[0])
+        ids = embedding.vertex_ids()
+        super().__init__(model, n_shape, n_exp, landmarks=embedding.remapped(ids), vertex_ids=ids)
+
+    def forward(self, shape_params=None, expression_params=None, pose_params=None, neck_pose=None, eye_pose=None):
+        return super().forward(shape_params, expression_params, pose_params, neck_pose, eye_pose)[1:]

@@ -225,6 +225,36 @@ int gif_flame_joints_f32(const float* J0, const float* Jdirs, const int32_t* par
                          const float* neck, int64_t ld_neck, const float* eye, int64_t ld_eye, float* A, float* coef, int B,
                          int KP, int J, gif_stream_t stream);
 
+/* FLAME landmarks: the public definition, smplx lbs.vertices2landmarks / find_dynamic_lmk_idx_and_bcoords as the
+ * FLAME layer of photometric_optimization uses them.
+ *   landmark[b,l] = sum_{i<3} bary[l,i] verts[b, vid[l,i]],  vid[l] = the three vertex ids of the landmark's embedding face.
+ * Tables (device memory, constants): st_vid [Ls][3] int32, st_bary [Ls][3] — one entry per static landmark; dyn_vid [R][Ld][3]
+ * int32, dyn_bary [R][Ld][3] — R = 2 M + 1 rows (FLAME: M = 39, R = 79, Ld = 17), one row chosen per sample:
+ *   Rw      = the world rotation of joint yaw_joint (the product of the rotations along the chain from it up to the root; FLAME:
+ *             joint 1, the neck) = the rotation part of A[b, yaw_joint] (A [B][J][12] row-major 3x4; Rw[i,0] = elements 0, 4, 8)
+ *   yaw_deg = -atan2(-Rw[2,0], sqrt(Rw[0,0]^2 + Rw[1,0]^2)) * 180 / pi
+ *   y       = round_half_even(min(yaw_deg, M))
+ *   row     = y if y >= 0 (-0 counts as 0), else 2 M if y < -M, else M - y;  a non-finite yaw selects row 0.
+ * The kernel clamps the row into 0..R-1, so it never indexes outside the table.  Vertex ids must lie in 0..V-1 (the Python layer
+ * checks the tables when it is built); an id outside contributes nothing, forward and backward.
+ *
+ * gif_flame_landmarks_f32: verts [B][V][3], A -> lmk [B][Ld + Ls][3] = cat(dynamic[row[b]], static) and row [B] int32 (may be
+ * null).  One launch; the row is chosen in the kernel, nothing is copied to the host.  B = 0 or Ld + Ls = 0: no-op.  J outside
+ * 1..8, yaw_joint outside 0..J-1, R even with Ld > 0, a null pointer with work to do: GIF_EINVAL.  R = 1 always selects row 0.
+ * With Ld = 0 neither A nor the dynamic tables are read (row = 0).
+ *
+ * gif_flame_landmarks_bwd_f32: g_lmk [B][Ld + Ls][3] = dL/d lmk and the forward's row -> g_verts [B][V][3] = dL/d verts.  EVERY
+ * element of g_verts is written (exact zeros where no landmark touches; Ld + Ls = 0 zero-fills).  Landmarks share vertices; the
+ * contributions to a vertex are summed in the order (landmark, corner), in LDS, by one lane: no float atomics, run-to-run
+ * identical bits.  B = 0 or V = 0: no-op.  The gradient goes to verts only: the row choice is piecewise constant, the tables are
+ * constants. */
+int gif_flame_landmarks_f32(const float* verts, const float* A, const int32_t* dyn_vid, const float* dyn_bary,
+                            const int32_t* st_vid, const float* st_bary, float* lmk, int32_t* row, int B, int V, int J,
+                            int yaw_joint, int R, int Ld, int Ls, gif_stream_t stream);
+int gif_flame_landmarks_bwd_f32(const float* g_lmk, const int32_t* row, const int32_t* dyn_vid, const float* dyn_bary,
+                                const int32_t* st_vid, const float* st_bary, float* g_verts, int B, int V, int R, int Ld, int Ls,
+                                gif_stream_t stream);
+
 /* Texture stealing — replaces FlameTextureSpace.compute_texture_map (model/stg2_generator.py:378-421):
  * per (sample, UV texel) barycentric 3-D point -> orthographic projection (y flipped) -> bilinear fetch of the source image
  * (grid_sample, zero padding, align_corners=False), and the normal-z visibility mask.  img [B,C,H,W] NCHW; verts/normals
