@@ -115,9 +115,9 @@ def batch_orth_proj(X, camera):
     return camera[:, :, 0:1] * X_trans
 
 
-def _rasterize_colors(vertices_ndc, faces, face_colors_of, h, w):
+def _rasterize_colors(vertices_ndc, faces, face_colors_of, h, w, with_depth=False):
     """The forward both attribute rasterisers share: (fv, fc, tri, image [B,3,h,w], mask [B,1,h,w]); `face_colors_of(faces_b)`
-    gives the per-face-corner attributes [B,F,3,3]."""
+    gives the per-face-corner attributes [B,F,3,3].  with_depth=True appends the depth buffer [B,h,w] (gif_amd.antialias)."""
     B = vertices_ndc.shape[0]
     faces_b = faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
     v = sr.to_image_space(vertices_ndc.float(), h, w)
@@ -125,7 +125,8 @@ def _rasterize_colors(vertices_ndc, faces, face_colors_of, h, w):
     fc = face_colors_of(faces_b)
     depth, tri, img = sr.new_buffers(B, h, w, vertices_ndc.device)
     sr.standard_rasterize_colors(fv, fc, depth, tri, img, h, w)
-    return fv, fc, tri, img.permute(0, 3, 1, 2).contiguous(), (tri >= 0)[:, None]
+    out = (fv, fc, tri, img.permute(0, 3, 1, 2).contiguous(), (tri >= 0)[:, None])
+    return out + (depth,) if with_depth else out
 
 
 def _rasterize_colors_bwd(fv, fc, tri, gimg, faces, V, vdtype, h, w, need_v, need_c, what):
@@ -188,7 +189,8 @@ def rasterize_attributes(vertices_ndc, faces, attributes, h, w):
     """Barycentric interpolation of per-vertex attributes [B,V,3] over the z-buffered mesh -> images [B,3,h,w], plus
     the coverage mask [B,1,h,w].  vertices_ndc: x,y in [-1,1], any z (visibility.py:38-44 conventions).
     Differentiable with respect to vertices_ndc (x, y) and attributes inside each pixel's winning face
-    (gif_rasterize_colors_bwd_f32); no silhouette, occlusion-boundary or depth gradient.  The mask has no gradient."""
+    (gif_rasterize_colors_bwd_f32); no silhouette, occlusion-boundary or depth gradient.  The mask has no gradient.
+    gif_amd.antialias.rasterize_attributes_aa is the opt-in variant whose outline carries a gradient."""
     return _RasterizeAttributesFn.apply(vertices_ndc, attributes, faces, h, w)
 
 

@@ -166,7 +166,8 @@ int gif_rasterize_colors_f64(const double* face_vertices, const double* face_col
  *   grad_face_colors   [B,F,3,3]: sum over the face's pixels of w_k * g
  *   grad_face_vertices [B,F,3,3]: x, y = sum over the face's pixels of sum_k (g . c_k) dw_k/dp_j; z = 0
  * with the barycentrics w recomputed from face_vertices by the forward's formula (inverDeno = 0: w constant, no vertex
- * gradient).  The gradient lives inside the winning face only: no silhouette or occlusion-boundary terms.  Either output
+ * gradient).  The gradient lives inside the winning face only: no silhouette or occlusion-boundary terms (gif_antialias_f32
+ * below is the opt-in post-pass that lets the outline carry one).  Either output
  * may be null (not written).  Deterministic: per (face, 64-row band of its bounding box) partial sums in a fixed order, then a
  * per-face sum over the bands in band order; no float atomics.  `workspace`: gif_rasterize_colors_bwd_workspace_bytes(B, F,
  * H, W) bytes, 4-byte aligned, no initialisation needed. */
@@ -191,6 +192,36 @@ int gif_vertex_normals_bwd_f32(const float* verts, const int32_t* faces, const i
  * grad_vertex[b,v] = sum over v's CSR entries (face*4 + corner) of grad_face[b,face,corner], in CSR order (no atomics). */
 int gif_face_gather_bwd_f32(const float* grad_face, const int32_t* csr_off, const int32_t* csr_ent, float* grad_vertex,
                             int B, int V, int F, gif_stream_t stream);
+
+/* Analytic edge antialiasing (silhouette gradients; no counterpart in the reference).  A post-pass over what
+ * gif_rasterize_colors_f32 left: image [B,C,H,W] (any C >= 1), tri [B,H,W] (background -1), depth [B,H,W], face_vertices [B,F,3,3]
+ * in pixel units, and edge_adj [F,3] int32 (one topology for the batch).  Pixel centres are the integer coordinates.
+ *   Edges.  Edge k of face f joins corners (k+1)%3 and (k+2)%3.  edge_adj[f,k] is the one other face with that undirected vertex
+ *     pair, -1 if there is none or more than one.  Edge k of f is a SILHOUETTE edge in image b if edge_adj[f,k] < 0 or that
+ *     neighbour fails the rasteriser's front-face test (y2-y0)(x1-x0) < (y1-y0)(x2-x0) on its own face_vertices[b].
+ *   Pairs.  A pixel p and its right or lower neighbour q, both in the image, with tri[p] != tri[q].  Front pixel A = p if
+ *     tri[q] < 0, or if tri[p] >= 0 and depth[p] <= depth[q]; else A = q.  B is the other; f = tri[A].
+ *   Crossing.  For each silhouette edge (P, Q) of f, k = 0, 1, 2: horizontal pair: t = (A.y - P.y) / (Q.y - P.y),
+ *     x* = P.x + t (Q.x - P.x), a = (x* - A.x)(B.x - A.x); vertical pair: x and y swapped.  An exactly zero denominator skips the
+ *     edge.  Candidates have 0 <= t <= 1 and 0 <= a <= 1; the smallest a wins, the lowest k on a tie; no candidate: nothing.
+ *   Blend (reads from `image` only).  a < 0.5: receiver A, donor B, weight 0.5 - a; else receiver B, donor A, weight a - 0.5;
+ *     out[receiver] += weight * (image[donor] - image[receiver]), a pixel's up to four pairs added in the order left, right, upper,
+ *     lower; out = image everywhere else.  out must not alias image.
+ * Gradients: to image through receiver and donor; to x, y of the two endpoints of the chosen edge through a; none through z,
+ * depth, the front choice, the silhouette classification or the candidate choice.
+ * gif_antialias_bwd_f32: grad_out [B,C,H,W] -> grad_image [B,C,H,W] and / or grad_face_vertices [B,F,3,3] (x, y of at most two
+ * corners per pair; z = 0; zeros for faces without pairs).  Either output may be null: it is not computed (image and workspace
+ * are needed for the vertex gradient only).  a is recomputed from the inputs.  Deterministic, no float atomics: per pixel
+ * gathers, and for the faces per (face, 64-row band of its bounding box) partial sums in a fixed order, then the bands in band
+ * order.  `workspace`: gif_antialias_bwd_workspace_bytes(B, F, H, W) bytes, 4-byte aligned, no initialisation needed.
+ * B = 0, or F = 0 (out = image, grad_image = grad_out where the pointers are given), returns 0; C < 1 or a negative size is
+ * GIF_EINVAL before any launch. */
+int gif_antialias_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+                      const int32_t* edge_adj, float* out, int B, int C, int F, int H, int W, gif_stream_t stream);
+int64_t gif_antialias_bwd_workspace_bytes(int B, int F, int H, int W);
+int gif_antialias_bwd_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+                          const int32_t* edge_adj, const float* grad_out, float* grad_image, float* grad_face_vertices, int B,
+                          int C, int F, int H, int W, void* workspace, gif_stream_t stream);
 
 /* The FLAME layer (blend shapes, pose correctives, linear blend skinning).  The published algorithm in the smplx
  * formulation; the reference keeps its layer in an absent submodule, so there is no line to cite.  Constants of a model with V
