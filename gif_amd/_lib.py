@@ -72,6 +72,8 @@ PROTOTYPES = {
     "gif_antialias_f32": (c_int, [P] * 6 + [c_int] * 5 + [P]),
     "gif_antialias_bwd_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "gif_antialias_bwd_f32": (c_int, [P] * 8 + [c_int] * 5 + [P, P]),
+    "gif_antialias_walk_f32": (c_int, [P] * 6 + [c_int] * 6 + [P]),
+    "gif_antialias_walk_bwd_f32": (c_int, [P] * 8 + [c_int] * 6 + [P, P]),
     "gif_flame_skin_f32": (c_int, [P] * 7 + [c_int] * 4 + [P]),
     "gif_flame_skin_bwd_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "gif_flame_skin_bwd_f32": (c_int, [P] * 7 + [c_int] * 4 + [P, P]),

@@ -6,6 +6,10 @@ and blends them by the edge's sub-pixel position, a smooth function of the edge'
 gradient.  Opt-in: rasterize_attributes and render_condition are unchanged (GIF's condition is floor-quantised to 8 bits and is
 the parity surface).
 Kernels: gif_antialias_f32, gif_antialias_bwd_f32 (gfx950, deterministic, no float atomics) behind the C ABI; no CPU fallback.
+
+max_hops > 0 lets a pair walk from the front pixel's face across non-silhouette edges to the face that owns the
+outline edge, through gif_antialias_walk_f32 and gif_antialias_walk_bwd_f32: on a mesh whose faces next to the outline are
+narrower than a pixel most of the outline blends only this way.  The default 0 takes the entry points above.
 """
 import numpy as np
 import torch
@@ -55,6 +59,15 @@ def edge_adjacency(faces):
     return cached[1]
 
 
+MAX_HOPS = 64
+
+
+def _check_hops(max_hops, what):
+    if isinstance(max_hops, bool) or not isinstance(max_hops, (int, np.integer)) or not 0 <= max_hops <= MAX_HOPS:
+        raise _lib.GifHipError(f"{what}: max_hops must be an integer in 0 .. {MAX_HOPS}, got {max_hops!r}")
+    return int(max_hops)
+
+
 def _one_topology(faces, B, what):
     if faces.ndimension() == 3 and B > 1 and faces.stride(0) != 0 and not torch.equal(faces, faces[:1].expand_as(faces)):
         raise _lib.GifHipError(f"{what} needs one face topology for the whole batch")
@@ -62,7 +75,7 @@ def _one_topology(faces, B, what):
 
 class _AntialiasFn(Function):
     @staticmethod
-    def forward(ctx, image, vertices_ndc, tri, depth, faces):
+    def forward(ctx, image, vertices_ndc, tri, depth, faces, max_hops):
         B, C, h, w = image.shape
         _one_topology(faces, B, "antialias")
         faces_b = faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
@@ -73,11 +86,14 @@ class _AntialiasFn(Function):
         tri, depth = tri.contiguous(), depth.float().contiguous()
         out = torch.empty_like(img)
         with torch.cuda.device(img.device):  # launch on the operands' device and its current stream
-            _lib.check(_lib.load().gif_antialias_f32(img.data_ptr(), tri.data_ptr(), depth.data_ptr(), fv.data_ptr(),
-                                                     adj.data_ptr(), out.data_ptr(), B, C, F, h, w,
-                                                     torch.cuda.current_stream().cuda_stream), "antialias")
+            args = (img.data_ptr(), tri.data_ptr(), depth.data_ptr(), fv.data_ptr(), adj.data_ptr(), out.data_ptr(), B, C, F, h, w)
+            stream = torch.cuda.current_stream().cuda_stream
+            if max_hops == 0:
+                _lib.check(_lib.load().gif_antialias_f32(*args, stream), "antialias")
+            else:
+                _lib.check(_lib.load().gif_antialias_walk_f32(*args, max_hops, stream), "antialias_walk")
         ctx.save_for_backward(img, tri, depth, fv, adj)
-        ctx.faces, ctx.V = faces, vertices_ndc.shape[1]
+        ctx.faces, ctx.V, ctx.max_hops = faces, vertices_ndc.shape[1], max_hops
         ctx.dtypes = (image.dtype, vertices_ndc.dtype)
         return out.to(image.dtype)
 
@@ -89,7 +105,7 @@ class _AntialiasFn(Function):
         F = fv.shape[1]
         need_i, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_i or need_v):
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         dev = img.device
         lib = _lib.load()
         g = gout.float().contiguous()
@@ -99,10 +115,13 @@ class _AntialiasFn(Function):
                          dtype=torch.float32)
         gv = None
         with torch.cuda.device(dev):
-            _lib.check(lib.gif_antialias_bwd_f32(img.data_ptr(), tri.data_ptr(), depth.data_ptr(), fv.data_ptr(), adj.data_ptr(),
-                                                 g.data_ptr(), gi.data_ptr() if need_i else None,
-                                                 gfv.data_ptr() if need_v else None, B, C, F, h, w, ws.data_ptr(),
-                                                 torch.cuda.current_stream().cuda_stream), "antialias_bwd")
+            args = (img.data_ptr(), tri.data_ptr(), depth.data_ptr(), fv.data_ptr(), adj.data_ptr(), g.data_ptr(),
+                    gi.data_ptr() if need_i else None, gfv.data_ptr() if need_v else None, B, C, F, h, w)
+            stream = torch.cuda.current_stream().cuda_stream
+            if ctx.max_hops == 0:
+                _lib.check(lib.gif_antialias_bwd_f32(*args, ws.data_ptr(), stream), "antialias_bwd")
+            else:
+                _lib.check(lib.gif_antialias_walk_bwd_f32(*args, ctx.max_hops, ws.data_ptr(), stream), "antialias_walk_bwd")
             if need_v:
                 if F == 0:
                     gv = torch.zeros((B, ctx.V, 3), device=dev, dtype=ctx.dtypes[1])
@@ -112,14 +131,16 @@ class _AntialiasFn(Function):
                     # to_image_space: x * w/2 + w/2, y * h/2 + h/2; z only orders the faces (no gradient)
                     gv *= torch.tensor([w / 2, h / 2, 0.0], device=dev, dtype=torch.float32)
                     gv = gv.to(ctx.dtypes[1])
-        return (gi.to(ctx.dtypes[0]) if need_i else None), gv, None, None, None
+        return (gi.to(ctx.dtypes[0]) if need_i else None), gv, None, None, None, None
 
 
-def antialias(image, tri, depth, vertices_ndc, faces):
+def antialias(image, tri, depth, vertices_ndc, faces, max_hops=0):
     """image [B,C,h,w] (any C >= 1) with the rasteriser's tri [B,h,w] int32 and depth [B,h,w] for vertices_ndc [B,V,3] and faces
     [F,3] or [B,F,3] (one topology) -> [B,C,h,w]: pixel pairs that straddle a silhouette edge blended by the edge's sub-pixel
     position (definition: include/gif_hip.h).  Differentiable with respect to image and to x, y of
-    vertices_ndc; not twice."""
+    vertices_ndc; not twice.  max_hops (0 .. 64) > 0: a pair whose front face does not own the outline edge walks on across up to
+    that many non-silhouette edges to the face that does; 0 is §3o's definition and its kernels."""
+    max_hops = _check_hops(max_hops, "antialias")
     for name, t in (("image", image), ("tri", tri), ("depth", depth), ("vertices_ndc", vertices_ndc), ("faces", faces)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise _lib.GifHipError(f"antialias needs device tensors (no CPU fallback): {name}")
@@ -129,7 +150,7 @@ def antialias(image, tri, depth, vertices_ndc, faces):
         raise _lib.GifHipError(f"tri must be int32, got {tri.dtype}")
     if vertices_ndc.ndimension() != 3 or vertices_ndc.shape[0] != image.shape[0] or vertices_ndc.shape[2] != 3:
         raise _lib.GifHipError("antialias: vertices_ndc [B,V,3]")
-    return _AntialiasFn.apply(image, vertices_ndc, tri, depth, faces)
+    return _AntialiasFn.apply(image, vertices_ndc, tri, depth, faces, max_hops)
 
 
 class _RasterizeBuffersFn(Function):
@@ -162,21 +183,23 @@ class _RasterizeBuffersFn(Function):
         return gv, ga, None, None, None
 
 
-def rasterize_attributes_aa(vertices_ndc, faces, attributes, h, w):
+def rasterize_attributes_aa(vertices_ndc, faces, attributes, h, w, max_hops=0):
     """render.rasterize_attributes with an antialiased outline: (image_aa [B,3,h,w], coverage_aa [B,1,h,w]).  The rasteriser's
     launches, then `antialias` over the three attribute channels and the 0 / 1 mask as a fourth.  Both outputs are differentiable:
     inside the faces as rasterize_attributes is, and at silhouette edges through the blend — a loss on coverage_aa alone reaches
-    the vertices."""
+    the vertices.  max_hops: as in `antialias`."""
+    max_hops = _check_hops(max_hops, "rasterize_attributes_aa")
     if not vertices_ndc.is_cuda:
         raise _lib.GifHipError("rasterize_attributes_aa needs device tensors (no CPU fallback)")
     img, mask, tri, depth = _RasterizeBuffersFn.apply(vertices_ndc, attributes, faces, h, w)
-    out = antialias(torch.cat((img, mask.to(img.dtype)), dim=1), tri, depth, vertices_ndc, faces)
+    out = antialias(torch.cat((img, mask.to(img.dtype)), dim=1), tri, depth, vertices_ndc, faces, max_hops)
     return out[:, :3], out[:, 3:]
 
 
-def soft_silhouette(vertices_ndc, faces, h, w):
+def soft_silhouette(vertices_ndc, faces, h, w, max_hops=0):
     """coverage_aa [B,1,h,w] alone: one rasteriser pass for the face-index and depth buffers (no attribute gather), then `antialias`
-    over the 0 / 1 mask.  Differentiable with respect to x, y of vertices_ndc."""
+    over the 0 / 1 mask.  Differentiable with respect to x, y of vertices_ndc.  max_hops: as in `antialias`."""
+    max_hops = _check_hops(max_hops, "soft_silhouette")
     if not vertices_ndc.is_cuda:
         raise _lib.GifHipError("soft_silhouette needs device tensors (no CPU fallback)")
     B = vertices_ndc.shape[0]
@@ -186,4 +209,4 @@ def soft_silhouette(vertices_ndc, faces, h, w):
         depth, tri, bary = sr.new_buffers(B, h, w, vertices_ndc.device)
         sr.standard_rasterize(fv, depth, tri, bary, h, w)
         mask = (tri >= 0)[:, None].float()
-    return antialias(mask, tri, depth, vertices_ndc, faces)
+    return antialias(mask, tri, depth, vertices_ndc, faces, max_hops)

@@ -14,6 +14,12 @@
 //                  that one's text is pinned inside rasterize.hip (tests/test_cpu_wiring.py), and a second copy could drift, so
 //                  here EVERY (face, band) partial is written — zeros where the box misses the band — and all are added.
 // FP contraction is off: t, a and the front-face test decide branches, and a float32 run of the definition must decide alike.
+//
+// The WALKING variants (gif_antialias_walk_f32 and its backward) are the same kernels with WALK = true: a pair is
+// then aa_pair_walk, which goes on from tri[A] across non-silhouette edges, at most max_hops times, to the face that owns the
+// outline edge.  The hit's face need no longer be tri[A], so the vertex-gradient wave of face g walks g's bounding box grown by
+// one pixel (A lies at most one pixel from the crossing point on g's edge), evaluates the pairs of every covered pixel in it and
+// keeps those whose front pixel it stands on and whose hit face is g.  WALK = false: the kernels described above, nothing else.
 #include "common.h"
 #include "raster_common.h"
 
@@ -68,6 +74,64 @@ __device__ __forceinline__ bool aa_pair(const float* __restrict__ depth, const f
     return hit;
 }
 
+// aa_pair with the walk of DESIGN.md §3p: where the face `cur` (first tri[A]) has no silhouette edge among its candidates, leave it
+// through the candidate nearest to A and ask the neighbour, at most max_hops times; the edge the walk came in through is left
+// out; reaching tri[B] ends the walk with nothing (no outline between the two pixels).  h.f is the face that owns the hit edge.
+// With max_hops = 0 this makes aa_pair's operations in aa_pair's order.  No array is indexed by a run-time value: no scratch.
+__device__ __forceinline__ bool aa_pair_walk(const float* __restrict__ depth, const float* __restrict__ fv,
+                                             const int32_t* __restrict__ adj, int F, int W, int px, int py, int axis, int tp, int tq,
+                                             int max_hops, AaHit& h) {
+    const int qx = px + (axis == 0 ? 1 : 0), qy = py + (axis == 0 ? 0 : 1);
+    bool a_is_p;
+    if (tq < 0) a_is_p = true;
+    else if (tp < 0) a_is_p = false;
+    else a_is_p = depth[(long)py * W + px] <= depth[(long)qy * W + qx];
+    const int f = a_is_p ? tp : tq, tb = a_is_p ? tq : tp;
+    if (f < 0 || f >= F) return false;
+    const int ax = a_is_p ? px : qx, ay = a_is_p ? py : qy;
+    const float Au = (float)(axis == 0 ? ax : ay), Av = (float)(axis == 0 ? ay : ax);
+    const float s = a_is_p ? 1.f : -1.f;
+    h.s = s; h.a_is_p = a_is_p;
+    int cur = f, prev = -1;
+    for (int hop = 0;; ++hop) {
+        const Face<float> fc = load_face(fv + (long)cur * 9);
+        const float X[3] = {fc.x0, fc.x1, fc.x2}, Y[3] = {fc.y0, fc.y1, fc.y2};
+        bool hit = false, leaves = false;  // a silhouette candidate; any other candidate (the way on)
+        float best = 0.f, lbest = 0.f;
+        int next = -1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int i = (k + 1) % 3, j = (k + 2) % 3;
+            const int n = adj[(long)cur * 3 + k];
+            if (hop > 0 && n == prev) continue;  // the edge the walk came in through
+            const float Pu = axis == 0 ? X[i] : Y[i], Pv = axis == 0 ? Y[i] : X[i];
+            const float Qu = axis == 0 ? X[j] : Y[j], Qv = axis == 0 ? Y[j] : X[j];
+            const float den = Qv - Pv;
+            if (den == 0.f) continue;
+            const float t = (Av - Pv) / den;
+            const float du = Qu - Pu;
+            const float us = Pu + t * du;
+            const float a = (us - Au) * s;
+            if (!(t >= 0.f && t <= 1.f && a >= 0.f && a <= 1.f)) continue;
+            if (hit && !(a < best)) continue;  // neither a nearer silhouette edge nor, after a hit, of any use as the way on
+            if (n >= 0 && n < F && front_facing(load_face(fv + (long)n * 9))) {  // not a silhouette edge in this image
+                if (hit || (leaves && !(a < lbest))) continue;  // smallest a; the lowest k keeps a tie
+                leaves = true;
+                lbest = a;
+                next = n;
+                continue;
+            }
+            hit = true;
+            best = a;
+            h.a = a; h.t = t; h.den = den; h.du = du; h.k = k;
+        }
+        if (hit) { h.f = cur; return true; }
+        if (!leaves || hop >= max_hops || next == tb) return false;
+        prev = cur;
+        cur = next;
+    }
+}
+
 // receiver / weight of a hit: a < 0.5: A receives from B with 0.5 - a, else B receives from A with a - 0.5
 __device__ __forceinline__ bool aa_receiver_is_a(const AaHit& h) { return h.a < 0.5f; }
 __device__ __forceinline__ float aa_weight(const AaHit& h) { return h.a < 0.5f ? 0.5f - h.a : h.a - 0.5f; }
@@ -90,11 +154,12 @@ __device__ __forceinline__ AaNeighbour aa_neighbour(int i) {
 }
 
 // BWD = false: out = antialias(image).  BWD = true: `image` is grad_out and `out` is grad_image (the transposed gather).
-template <bool BWD>
+// WALK: pairs are aa_pair_walk's with max_hops (else max_hops is not read).
+template <bool BWD, bool WALK>
 __global__ void __launch_bounds__(kAaThreads)
 aa_gather(const float* __restrict__ image, const int32_t* __restrict__ tri, const float* __restrict__ depth,
           const float* __restrict__ fv, const int32_t* __restrict__ adj, float* __restrict__ out, long npix, int C, int F, int H,
-          int W) {
+          int W, int max_hops) {
     const long gp = (long)blockIdx.x * kAaThreads + threadIdx.x;
     if (gp >= npix) return;
     const long hw = (long)H * W;
@@ -116,8 +181,10 @@ aa_gather(const float* __restrict__ image, const int32_t* __restrict__ tri, cons
         const int tother = tb[(long)oy * W + ox];
         if (tother == tme) continue;
         AaHit h;
-        const bool ok = nb.me_first ? aa_pair(depth + b * hw, fv + (long)b * F * 9, adj, F, W, x, y, nb.axis, tme, tother, h)
-                                    : aa_pair(depth + b * hw, fv + (long)b * F * 9, adj, F, W, ox, oy, nb.axis, tother, tme, h);
+        const int qx = nb.me_first ? x : ox, qy = nb.me_first ? y : oy;  // the pair's first pixel and the two face indices
+        const int t0 = nb.me_first ? tme : tother, t1 = nb.me_first ? tother : tme;
+        const bool ok = WALK ? aa_pair_walk(depth + b * hw, fv + (long)b * F * 9, adj, F, W, qx, qy, nb.axis, t0, t1, max_hops, h)
+                             : aa_pair(depth + b * hw, fv + (long)b * F * 9, adj, F, W, qx, qy, nb.axis, t0, t1, h);
         if (!ok) continue;
         const bool me_is_a = h.a_is_p == nb.me_first;
         self[i] = aa_receiver_is_a(h) == me_is_a;
@@ -151,10 +218,13 @@ constexpr int kAaBand = 64;   // rows per band: a wave walks at most 64 rows x W
 
 inline int aa_bands(int H) { return (H + kAaBand - 1) / kAaBand; }
 
+// WALK: the box is grown by one pixel on every side before it is clamped (not empty even where the face covers no pixel centre),
+// every covered pixel in it is a possible front pixel, and a pair counts for this wave if its hit face is fi.
+template <bool WALK>
 __global__ void __launch_bounds__(kAaWaves * 64)
 aa_bwd_band(const float* __restrict__ image, const int32_t* __restrict__ tri, const float* __restrict__ depth,
             const float* __restrict__ fv, const int32_t* __restrict__ adj, const float* __restrict__ g, float* __restrict__ part,
-            int C, int F, int H, int W, int bands) {
+            int C, int F, int H, int W, int bands, int max_hops) {
     const int lane = threadIdx.x & 63;
     const int fi = blockIdx.x * kAaWaves + (threadIdx.x >> 6), band = blockIdx.y, b = blockIdx.z;
     if (fi >= F) return;  // whole wave: fi is uniform across it
@@ -164,7 +234,16 @@ aa_bwd_band(const float* __restrict__ image, const int32_t* __restrict__ tri, co
     // the band's rows of the face's clamped bounding box; none for a face the rasteriser never lists (it wins no pixel) or a box
     // outside the band: the partial is written all the same (zeros), so the second pass needs no band range
     int x_min = 0, x_max = -1, y_min = 0, y_max = -1;
-    if (front_facing(f)) face_bbox(f, H, W, x_min, x_max, y_min, y_max);
+    if (front_facing(f)) {
+        if (!WALK) {
+            face_bbox(f, H, W, x_min, x_max, y_min, y_max);
+        } else {
+            x_min = max((int)ceil(fmin(f.x0, fmin(f.x1, f.x2))) - 1, 0);
+            x_max = min((int)floor(fmax(f.x0, fmax(f.x1, f.x2))) + 1, W - 1);
+            y_min = max((int)ceil(fmin(f.y0, fmin(f.y1, f.y2))) - 1, 0);
+            y_max = min((int)floor(fmax(f.y0, fmax(f.y1, f.y2))) + 1, H - 1);
+        }
+    }
     const int r0 = max(y_min, band * kAaBand), r1 = min(y_max, band * kAaBand + kAaBand - 1);
     const int cols = x_max - x_min + 1, n = (cols > 0 && r1 >= r0) ? (r1 - r0 + 1) * cols : 0;
     if (n == 0) {  // whole wave: n is uniform across it
@@ -181,7 +260,8 @@ aa_bwd_band(const float* __restrict__ image, const int32_t* __restrict__ tri, co
     for (int p = lane; p < n; p += 64) {
         const int y = r0 + p / cols, x = x_min + p % cols;
         const long me = (long)y * W + x;
-        if (tb[me] != fi) continue;
+        const int tme = WALK ? tb[me] : fi;
+        if (WALK ? tme < 0 : tb[me] != fi) continue;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const AaNeighbour nb = aa_neighbour(i);
@@ -189,11 +269,14 @@ aa_bwd_band(const float* __restrict__ image, const int32_t* __restrict__ tri, co
             if (ox < 0 || ox >= W || oy < 0 || oy >= H) continue;
             const long other = (long)oy * W + ox;
             const int tother = tb[other];
-            if (tother == fi) continue;
+            if (tother == tme) continue;
             AaHit h;
-            const bool ok = nb.me_first ? aa_pair(depth + b * hw, fvb, adj, F, W, x, y, nb.axis, fi, tother, h)
-                                        : aa_pair(depth + b * hw, fvb, adj, F, W, ox, oy, nb.axis, tother, fi, h);
-            if (!ok || h.a_is_p != nb.me_first) continue;  // this pixel is not the pair's front pixel: the other face's wave has it
+            const int qx = nb.me_first ? x : ox, qy = nb.me_first ? y : oy;  // the pair's first pixel and the two face indices
+            const int t0 = nb.me_first ? tme : tother, t1 = nb.me_first ? tother : tme;
+            const bool ok = WALK ? aa_pair_walk(depth + b * hw, fvb, adj, F, W, qx, qy, nb.axis, t0, t1, max_hops, h)
+                                 : aa_pair(depth + b * hw, fvb, adj, F, W, qx, qy, nb.axis, t0, t1, h);
+            // not the pair's front pixel: the pair is counted where its front pixel is; WALK: another face owns the hit edge
+            if (!ok || h.a_is_p != nb.me_first || (WALK && h.f != fi)) continue;
             const bool recv_a = aa_receiver_is_a(h);
             const long r = recv_a ? me : other, d = recv_a ? other : me;
             float dot = 0.f;
@@ -253,6 +336,75 @@ int aa_check_dims(const char* who, int B, int C, int F, int H, int W) {
     return 0;
 }
 
+constexpr int kAaMaxHops = 64;
+
+// max_hops < 0: the pairs of aa_pair (gif_antialias_f32); else the walking pairs (gif_antialias_walk_f32)
+int aa_forward(const char* who, const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+               const int32_t* edge_adj, float* out, int B, int C, int F, int H, int W, int max_hops, gif_stream_t stream) {
+    if (B == 0) return 0;
+    hipStream_t s = gif::as_stream(stream);
+    if (F == 0) {  // no faces: no pairs
+        if (!image || !out) return 0;
+        hipError_t e = hipMemcpyAsync(out, image, (size_t)B * C * H * W * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) { gif::set_error("%s copy: %s", who, hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    GIF_REQUIRE(image && tri && depth && face_vertices && edge_adj && out, "%s: null pointer", who);
+    GIF_REQUIRE(image != out, "%s: out must not alias image", who);
+    const long npix = (long)B * H * W;
+    const unsigned grid = (unsigned)gif::cdiv(npix, kAaThreads);
+    if (max_hops < 0)
+        aa_gather<false, false><<<grid, kAaThreads, 0, s>>>(image, tri, depth, face_vertices, edge_adj, out, npix, C, F, H, W, 0);
+    else
+        aa_gather<false, true><<<grid, kAaThreads, 0, s>>>(image, tri, depth, face_vertices, edge_adj, out, npix, C, F, H, W,
+                                                           max_hops);
+    return gif::check_launch(who);
+}
+
+int aa_backward(const char* who, const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+                const int32_t* edge_adj, const float* grad_out, float* grad_image, float* grad_face_vertices, int B, int C, int F,
+                int H, int W, int max_hops, void* workspace, gif_stream_t stream) {
+    if (B == 0) return 0;
+    hipStream_t s = gif::as_stream(stream);
+    if (F == 0) {
+        if (!grad_out || !grad_image) return 0;
+        hipError_t e = hipMemcpyAsync(grad_image, grad_out, (size_t)B * C * H * W * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) { gif::set_error("%s copy: %s", who, hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    GIF_REQUIRE(tri && depth && face_vertices && edge_adj && grad_out, "%s: null pointer", who);
+    GIF_REQUIRE(grad_image || grad_face_vertices, "%s: no output", who);
+    GIF_REQUIRE(grad_image != grad_out, "%s: grad_image must not alias grad_out", who);
+    const int bands = aa_bands(H);
+    if (grad_face_vertices) {
+        GIF_REQUIRE(image && workspace, "%s: the vertex gradient needs image and workspace", who);
+        GIF_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: workspace must be 4-byte aligned", who);
+        GIF_REQUIRE(B <= 65535 && bands <= 65535 && (long)B * F * bands * kAaStride < (1L << 40), "%s: too many images / faces", who);
+    }
+    if (grad_image) {
+        const long npix = (long)B * H * W;
+        const unsigned grid = (unsigned)gif::cdiv(npix, kAaThreads);
+        if (max_hops < 0)
+            aa_gather<true, false><<<grid, kAaThreads, 0, s>>>(grad_out, tri, depth, face_vertices, edge_adj, grad_image, npix, C, F,
+                                                               H, W, 0);
+        else
+            aa_gather<true, true><<<grid, kAaThreads, 0, s>>>(grad_out, tri, depth, face_vertices, edge_adj, grad_image, npix, C, F,
+                                                              H, W, max_hops);
+    }
+    if (grad_face_vertices) {
+        float* part = reinterpret_cast<float*>(workspace);
+        const dim3 grid((unsigned)gif::cdiv(F, kAaWaves), (unsigned)bands, (unsigned)B);
+        if (max_hops < 0)
+            aa_bwd_band<false><<<grid, kAaWaves * 64, 0, s>>>(image, tri, depth, face_vertices, edge_adj, grad_out, part, C, F, H, W,
+                                                              bands, 0);
+        else
+            aa_bwd_band<true><<<grid, kAaWaves * 64, 0, s>>>(image, tri, depth, face_vertices, edge_adj, grad_out, part, C, F, H, W,
+                                                             bands, max_hops);
+        aa_bwd_reduce<<<gif::cdiv((long)B * F, 256), 256, 0, s>>>(part, grad_face_vertices, (long)B * F, bands);
+    }
+    return gif::check_launch(who);
+}
+
 }  // namespace
 
 extern "C" {
@@ -260,20 +412,15 @@ extern "C" {
 int gif_antialias_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
                       const int32_t* edge_adj, float* out, int B, int C, int F, int H, int W, gif_stream_t stream) {
     if (int rc = aa_check_dims("antialias", B, C, F, H, W)) return rc;
-    if (B == 0) return 0;
-    hipStream_t s = gif::as_stream(stream);
-    if (F == 0) {  // no faces: no pairs
-        if (!image || !out) return 0;
-        hipError_t e = hipMemcpyAsync(out, image, (size_t)B * C * H * W * sizeof(float), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { gif::set_error("antialias copy: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    GIF_REQUIRE(image && tri && depth && face_vertices && edge_adj && out, "antialias: null pointer");
-    GIF_REQUIRE(image != out, "antialias: out must not alias image");
-    const long npix = (long)B * H * W;
-    aa_gather<false><<<gif::cdiv(npix, kAaThreads), kAaThreads, 0, s>>>(image, tri, depth, face_vertices, edge_adj, out, npix, C, F,
-                                                                        H, W);
-    return gif::check_launch("antialias");
+    return aa_forward("antialias", image, tri, depth, face_vertices, edge_adj, out, B, C, F, H, W, -1, stream);
+}
+
+int gif_antialias_walk_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+                           const int32_t* edge_adj, float* out, int B, int C, int F, int H, int W, int max_hops,
+                           gif_stream_t stream) {
+    if (int rc = aa_check_dims("antialias_walk", B, C, F, H, W)) return rc;
+    GIF_REQUIRE(max_hops >= 0 && max_hops <= kAaMaxHops, "antialias_walk: max_hops %d outside 0 .. %d", max_hops, kAaMaxHops);
+    return aa_forward("antialias_walk", image, tri, depth, face_vertices, edge_adj, out, B, C, F, H, W, max_hops, stream);
 }
 
 int64_t gif_antialias_bwd_workspace_bytes(int B, int F, int H, int W) {
@@ -285,35 +432,16 @@ int gif_antialias_bwd_f32(const float* image, const int32_t* tri, const float* d
                           const int32_t* edge_adj, const float* grad_out, float* grad_image, float* grad_face_vertices, int B,
                           int C, int F, int H, int W, void* workspace, gif_stream_t stream) {
     if (int rc = aa_check_dims("antialias_bwd", B, C, F, H, W)) return rc;
-    if (B == 0) return 0;
-    hipStream_t s = gif::as_stream(stream);
-    if (F == 0) {
-        if (!grad_out || !grad_image) return 0;
-        hipError_t e = hipMemcpyAsync(grad_image, grad_out, (size_t)B * C * H * W * sizeof(float), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { gif::set_error("antialias_bwd copy: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    GIF_REQUIRE(tri && depth && face_vertices && edge_adj && grad_out, "antialias_bwd: null pointer");
-    GIF_REQUIRE(grad_image || grad_face_vertices, "antialias_bwd: no output");
-    GIF_REQUIRE(grad_image != grad_out, "antialias_bwd: grad_image must not alias grad_out");
-    const int bands = aa_bands(H);
-    if (grad_face_vertices) {
-        GIF_REQUIRE(image && workspace, "antialias_bwd: the vertex gradient needs image and workspace");
-        GIF_REQUIRE(((uintptr_t)workspace & 3) == 0, "antialias_bwd: workspace must be 4-byte aligned");
-        GIF_REQUIRE(B <= 65535 && bands <= 65535 && (long)B * F * bands * kAaStride < (1L << 40),
-                    "antialias_bwd: too many images / faces");
-    }
-    if (grad_image) {
-        const long npix = (long)B * H * W;
-        aa_gather<true><<<gif::cdiv(npix, kAaThreads), kAaThreads, 0, s>>>(grad_out, tri, depth, face_vertices, edge_adj, grad_image,
-                                                                           npix, C, F, H, W);
-    }
-    if (grad_face_vertices) {
-        float* part = reinterpret_cast<float*>(workspace);
-        aa_bwd_band<<<dim3((unsigned)gif::cdiv(F, kAaWaves), (unsigned)bands, (unsigned)B), kAaWaves * 64, 0, s>>>(
-            image, tri, depth, face_vertices, edge_adj, grad_out, part, C, F, H, W, bands);
-        aa_bwd_reduce<<<gif::cdiv((long)B * F, 256), 256, 0, s>>>(part, grad_face_vertices, (long)B * F, bands);
-    }
-    return gif::check_launch("antialias_bwd");
+    return aa_backward("antialias_bwd", image, tri, depth, face_vertices, edge_adj, grad_out, grad_image, grad_face_vertices, B, C, F,
+                       H, W, -1, workspace, stream);
+}
+
+int gif_antialias_walk_bwd_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+                               const int32_t* edge_adj, const float* grad_out, float* grad_image, float* grad_face_vertices, int B,
+                               int C, int F, int H, int W, int max_hops, void* workspace, gif_stream_t stream) {
+    if (int rc = aa_check_dims("antialias_walk_bwd", B, C, F, H, W)) return rc;
+    GIF_REQUIRE(max_hops >= 0 && max_hops <= kAaMaxHops, "antialias_walk_bwd: max_hops %d outside 0 .. %d", max_hops, kAaMaxHops);
+    return aa_backward("antialias_walk_bwd", image, tri, depth, face_vertices, edge_adj, grad_out, grad_image, grad_face_vertices, B,
+                       C, F, H, W, max_hops, workspace, stream);
 }
 }

@@ -222,6 +222,30 @@ int64_t gif_antialias_bwd_workspace_bytes(int B, int F, int H, int W);
 int gif_antialias_bwd_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
                           const int32_t* edge_adj, const float* grad_out, float* grad_image, float* grad_face_vertices, int B,
                           int C, int F, int H, int W, void* workspace, gif_stream_t stream);
+/* The same with a WALK to the outline edge across faces, for meshes whose faces next to the outline are narrower
+ * than a pixel: the outermost covered pixel then lies in a face that does not own the silhouette edge beside it.  Everything
+ * above stands; one parameter is added, 0 <= max_hops <= 64.  A pair starts with cur = f = tri[A], prev = none, hop = 0.
+ *   1. In face cur take the edges k = 0, 1, 2, from hop 1 on without those whose edge_adj[cur,k] == prev (the edge the walk came
+ *      in through); den, t, a as above (axis, sign, A.u and A.v are the pair's); a zero denominator skips the edge; the CANDIDATES
+ *      have 0 <= t <= 1 and 0 <= a <= 1.
+ *   2. If some candidates are silhouette edges, the one with the smallest a (lowest k on a tie) is the pair's hit: edge (cur, k)
+ *      with its a, t, den.  The walk ends.
+ *   3. Else take the candidate with the smallest a (lowest k on a tie), the edge through which the segment A -> B leaves cur.  No
+ *      candidate, or hop == max_hops: the pair blends nothing.  Else n = edge_adj[cur,k] (valid and front-facing, the edge being
+ *      no silhouette edge); n == tri[B]: the pair blends nothing (no outline between the two pixels); else prev = cur, cur = n,
+ *      hop += 1, and on with step 1.
+ * Blend, receiver and weight as above.  Gradients by the same formula to x, y of the hit edge's endpoints, corners (k+1)%3 and
+ * (k+2)%3 of face cur (which need not be tri[A]); none through z, depth, the front choice, the classification or the route.
+ * max_hops = 0 is the definition above word for word, and a pair that blends there blends identically for every max_hops: walking
+ * only adds blends.  The backward is deterministic without float atomics as above, per (face, 64-row band of its bounding box
+ * grown by one pixel).  Same contracts, null rules and empty-work rules as the two entry points above; max_hops outside 0 .. 64 is
+ * GIF_EINVAL before any launch.  `workspace`: gif_antialias_bwd_workspace_bytes serves both backward entry points. */
+int gif_antialias_walk_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+                           const int32_t* edge_adj, float* out, int B, int C, int F, int H, int W, int max_hops,
+                           gif_stream_t stream);
+int gif_antialias_walk_bwd_f32(const float* image, const int32_t* tri, const float* depth, const float* face_vertices,
+                               const int32_t* edge_adj, const float* grad_out, float* grad_image, float* grad_face_vertices, int B,
+                               int C, int F, int H, int W, int max_hops, void* workspace, gif_stream_t stream);
 
 /* The FLAME layer (blend shapes, pose correctives, linear blend skinning).  The published algorithm in the smplx
  * formulation; the reference keeps its layer in an absent submodule, so there is no line to cite.  Constants of a model with V

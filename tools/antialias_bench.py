@@ -8,7 +8,11 @@ C = 4 (three attribute channels and the mask, as rasterize_attributes_aa runs it
 Each figure is the median over `--calls` eager calls (after `--warmup`) of the time between two HIP events around one call, so it
 includes the gaps the host leaves between the launches of a call; at these sizes (tens of microseconds of kernel time) the
 function figures are mostly host time.  No time is required of the new kernels: there is no earlier version.
-Usage (GPU): python tools/antialias_bench.py [--batch 4] [--size 256] [--out profiles/antialias.txt]
+--max-hops H adds, next to those rows, the walking entry points gif_antialias_walk_f32 / gif_antialias_walk_bwd_f32 (DESIGN.md
+§3p) and the three functions at max_hops = H; the rows without a hop count in the same run are the yardstick for what walking
+costs.  --coverage adds how much of the outline blends at 0, 4, 8 and 16 hops, counted by the float64 restatement
+(tests/antialias_walk_ref.py) on the GPU's tri and depth buffers.
+Usage (GPU): python tools/antialias_bench.py [--batch 4] [--size 256] [--max-hops H] [--coverage] [--out profiles/antialias.txt]
 """
 import argparse
 import os
@@ -30,6 +34,8 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--calls", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--max-hops", type=int, default=None, help="also time the walking entry points and functions at this setting")
+    ap.add_argument("--coverage", action="store_true", help="count the outline pairs that blend at 0 / 4 / 8 / 16 hops")
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "antialias_bench needs an MI355X"
@@ -85,6 +91,25 @@ def main():
     def whole_ra():
         return torch.autograd.grad(render.rasterize_attributes(vg, ft, ag, h, w)[0], [vg, ag], G3)
 
+    hops = a.max_hops
+
+    def walk_fwd():
+        _lib.check(lib.gif_antialias_walk_f32(ptr(image), ptr(tri), ptr(depth), ptr(fv), ptr(adj), ptr(out), B, C, F, h, w, hops,
+                                              stream), "aa_walk")
+
+    def walk_bwd(need_i=True, need_v=True):
+        _lib.check(lib.gif_antialias_walk_bwd_f32(ptr(image), ptr(tri), ptr(depth), ptr(fv), ptr(adj), ptr(g4),
+                                                  ptr(gi) if need_i else None, ptr(gfv) if need_v else None, B, C, F, h, w, hops,
+                                                  ptr(ws_aa), stream), "aa_walk_bwd")
+
+    def whole_aa_walk():
+        i2, c2 = AA.rasterize_attributes_aa(vg, ft, ag, h, w, max_hops=hops)
+        return torch.autograd.grad([i2, c2], [vg, ag], [G3, g4[:, 3:]])
+
+    def sil_walk(max_hops):
+        vs = vt.clone().requires_grad_(True)
+        return lambda: torch.autograd.grad(AA.soft_silhouette(vs, ft, h, w, max_hops=max_hops), vs, g4[:, 3:])
+
     arms = [
         ("gif_antialias_f32", aa_fwd),
         ("gif_antialias_bwd_f32 (image + vertices)", aa_bwd),
@@ -99,9 +124,26 @@ def main():
         ("rasterize_attributes() fwd + bwd", whole_ra),
         ("rasterize_attributes_aa() fwd + bwd", whole_aa),
     ]
+    if hops is not None:
+        o_walk = AA.antialias(ig, tri, depth, vg, ft, max_hops=hops)
+        tag = f"max_hops={hops}"
+        arms += [
+            (f"gif_antialias_walk_f32, {tag}", walk_fwd),
+            (f"gif_antialias_walk_bwd_f32 (image + vertices), {tag}", walk_bwd),
+            (f"gif_antialias_walk_bwd_f32 (image only), {tag}", lambda: walk_bwd(True, False)),
+            (f"gif_antialias_walk_bwd_f32 (vertices only), {tag}", lambda: walk_bwd(False, True)),
+            (f"antialias({tag}) forward", lambda: AA.antialias(ig, tri, depth, vg, ft, max_hops=hops)),
+            (f"antialias({tag}) backward", lambda: torch.autograd.grad(o_walk, [ig, vg], g4, retain_graph=True)),
+            (f"rasterize_attributes_aa({tag}) fwd + bwd", whole_aa_walk),
+            ("soft_silhouette() fwd + bwd", sil_walk(0)),
+            (f"soft_silhouette({tag}) fwd + bwd", sil_walk(hops)),
+        ]
     pairs = int(((tri[:, :, 1:] != tri[:, :, :-1]).sum() + (tri[:, 1:] != tri[:, :-1]).sum()).item())
     aa_fwd()
     moved = int((out != image).any(1).sum().item())
+    if hops is not None:
+        walk_fwd()
+        moved_walk = int((out != image).any(1).sum().item())
     res = {}
     for _ in range(2):  # two alternating passes; the second is reported (clocks and caches settled)
         for name, fn in arms:
@@ -110,9 +152,23 @@ def main():
              f"{pairs} pixel pairs with different faces, {moved} pixels changed by the blend, "
              f"coverage {(tri >= 0).float().mean().item():.3f}",
              f"median of {a.calls} eager calls after {a.warmup} warm-up calls, HIP events around each call (10th .. 90th percentile)"]
+    if hops is not None:
+        lines.insert(2, f"{moved_walk} pixels changed by the blend with max_hops = {hops}")
     for name, _ in arms:
         m, lo, hi = res[name]
-        lines.append(f"{name:44s} {m * 1e3:9.1f} us  ({lo * 1e3:.1f} .. {hi * 1e3:.1f})")
+        lines.append(f"{name:60s} {m * 1e3:9.1f} us  ({lo * 1e3:.1f} .. {hi * 1e3:.1f})")
+    if a.coverage:
+        import antialias_ref as aref
+        import antialias_walk_ref as wref
+        cov = (tri >= 0)[:, None].double().cpu()
+        fv64 = aref.face_vertices_ref(vt.cpu().double(), sr.to_image_space(vt, h, w).cpu(), f, h, w)
+        adj64 = aref.edge_adjacency_ref(f)
+        lines.append("coverage of the outline (float64 restatement on the GPU's tri and depth, coverage as the image, all images):")
+        for n in (0, 4, 8, 16):
+            o, st = wref.antialias_walk_ref(cov, tri.cpu(), depth.cpu(), fv64, adj64, n)
+            lines.append(f"  max_hops = {n:2d}: {st['outline_pairs']} outline pairs, {int(st['hits'][:, 7].sum())} of them blend; "
+                         f"{st['blended']} of all {st['pairs']} pairs blend, {st['marginal']} marginal; "
+                         f"{int((o != cov).sum())} pixels changed")
     text = "\n".join(lines)
     print(text, flush=True)
     if a.out:
