@@ -101,8 +101,7 @@ int reduce_partials(const float* partial, float* out, int Y, int nblk, int C, fl
 inline int64_t epilogue_ws_rows(int64_t rows) { return 2 * (rows / 64 + 16) + 4096 + 64; }
 
 // ---- Winograd transforms (conv_winograd.hip), shared with the Winograd wgrad in conv_wgrad.hip ----
-// padded dims of a transformed operand [16][ntiles_pad][CP]
-void winograd_padded_dims(long ntiles, int C, long* ntiles_pad, int* CP);
+// (padded dims of a transformed operand [16][ntiles_pad][CP]: wino_route.h padded_tiles / padded_channels)
 // V = B^T d B per 4x4 input patch (x [B,H,W,C], optional per-sample channel scale [B,C])
 int winograd_input_transform(const float* x, const float* scale, float* V, int B, int H, int W, int C, hipStream_t s);
 // Mg = G g G^T per 2x2 tile of gy [B,H,W,C] (F(3x3,2x2) "filter" transform of the output gradient)
@@ -234,7 +233,7 @@ __device__ __forceinline__ void split_pair_h2(const float a0, const float a1, co
 }
 // header of an f16x2 weight packing: int32 exponents of the RP rows, then RP int32 row flags ("a 16-element K group of this row
 // lies outside the window": launches that use the row take the bf16x3 fallback); the f16 planes follow.
-inline size_t h2_header_bytes(int RP) { return (size_t)2 * RP * sizeof(int); }
+constexpr size_t h2_header_bytes(int RP) { return (size_t)2 * RP * sizeof(int); }
 // gate words of the guarded launches (runtime.hip).  Eager launches: a ring of device words and a generation counter — the f16x2
 // kernel raises its gate with atomicMax(gate, gen), the fallback launch runs iff *gate >= gen; a word is reused 65536 guarded launches
 // later under a larger gen, and generations only grow, so nothing is ever reset and streams do not matter.  (">=", round 6: should a

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "wgrad_route.h"  // which kernel a call gets: every tile / stage / twin / family decision of the host code below
+#include "wino_route.h"   // padded dims of the Winograd transforms' outputs
 
 namespace {
 
@@ -1875,11 +1876,9 @@ static int conv3x3_winograd_wgrad_impl(const float* x, const float* gy, float* V
     GIF_REQUIRE(Cs > 0 && Cb > 0 && Cs % 4 == 0 && Cb % 4 == 0, "winograd_wgrad: channels must be multiples of 4");
     hipStream_t s = gif::as_stream(stream);
     const long ntiles = (long)B * (H / 2) * (W / 2);
-    int CsP = 0, CbP = 0;
-    long ntiles_pad = 0;
-    gif::winograd_padded_dims(ntiles, Cs, &ntiles_pad, &CsP);
-    gif::winograd_padded_dims(ntiles, Cb, &ntiles_pad, &CbP);
-    GIF_REQUIRE(ntiles_pad * CsP < (1L << 31) && ntiles_pad * CbP < (1L << 31), "winograd_wgrad: tensor too large for 32-bit offsets");
+    const int CsP = gif_wino::padded_channels(Cs), CbP = gif_wino::padded_channels(Cb);
+    const long ntiles_pad = gif_wino::padded_tiles(ntiles);
+    GIF_REQUIRE(gif_wino::fits_i32(ntiles_pad * CsP) && gif_wino::fits_i32(ntiles_pad * CbP), "winograd_wgrad: tensor too large for 32-bit offsets");
     double flops = 2.0 * B * H * W * 9.0 * Cs * Cb;  // ALGORITHMIC (direct) FLOPs
     {
         gif::ProfScope prof_t(4, 4.0 * ((double)B * H * W * ((x ? Cb : 0) + Cs) + 16.0 * ntiles_pad * ((x ? CbP : 0) + CsP)), s,

@@ -19,6 +19,9 @@
 #include <string.h>
 
 #include "common.h"
+#include "wino_route.h"  // which kernels a call gets and every padded size: every decision of the host code below
+
+namespace route = gif_wino;
 
 namespace {
 
@@ -33,9 +36,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return base + idx;
 }
 
-// GEMM tile: 256 threads = 4 waves as 2 (M) x 2 (N); wave tile 64 tiles x 32 couts; block tile 128 x 64; BK = 32.
-constexpr int WBM = 128, WBN = 64, WBK = 32, WNSTAGE = 3;
-constexpr int WPAD = 256;  // row padding of the V / Mg planes: the bf16x3 GEMM walks them in 256-row blocks
+// GEMM tile: 256 threads = 4 waves as 2 (M) x 2 (N); wave tile 64 tiles x 32 couts; block tile 128 x 64; BK = 32 (wino_route.h)
+using route::WBM, route::WBN, route::WBK, route::WNSTAGE;
+using route::WPAD;  // row padding of the V / Mg planes: the bf16x3 GEMM walks them in 256-row blocks
 
 // ------------------------------------------------------------------------------------------------ input transform
 // one lane = one 4x4 input patch of one tile x 4 channels; B^T d B with B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1].
@@ -1187,83 +1190,37 @@ __global__ void wino_weight_transform_x3(const float* __restrict__ w, unsigned s
 
 }  // namespace
 
+// ---- host side: knobs -> route (wino_route.h) -> fill -> launch ---------------------------------------------------------------------
+static_assert(gif::h2_header_bytes(128) == route::h2_header_bytes(128), "wino_route.h sizes the f16x2 transformed weight");
+
+// The GIF_* variables of wino_route.h, read once per process.
+static const route::WinoKnobs& wino_knobs() {
+    static const route::WinoKnobs once = route::parse_knobs(gif::knob("GIF_WINO_XFORM"), gif::knob("GIF_WINO_WN"), gif::knob("GIF_WINO_X3_TILE"),
+                                                            gif::knob("GIF_WINO_H2_STAGES"));
+    return once;
+}
+
 namespace gif {
 
-void winograd_padded_dims(long ntiles, int C, long* ntiles_pad, int* CP) {
-    *ntiles_pad = (ntiles + WPAD - 1) / WPAD * WPAD;
-    *CP = (C + WBK - 1) / WBK * WBK;
-}
-
-static unsigned transform_blocks(long total) {
-    long blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    return (unsigned)blocks;
-}
-
 int winograd_input_transform(const float* x, const float* scale, float* V, int B, int H, int W, int C, hipStream_t s) {
-    const long ntiles = (long)B * (H / 2) * (W / 2);
-    long ntiles_pad;
-    int CP;
-    winograd_padded_dims(ntiles, C, &ntiles_pad, &CP);
-    // The vertical-reuse variant with 8 tiles per lane is the default (profiles/r4_wino_transform_rows.txt: 23.8 -> 23.0 ms/step, HBM bytes
-    // of the transform family 1.10x -> 1.065x the algorithmic count); GIF_WINO_XFORM=tile selects the one-patch-per-lane kernel,
-    // rows4 / rows16 the other depths (A/B).
-    static const int rows = [] {
-        const char* e = gif::knob("GIF_WINO_XFORM");
-        if (!e) return 8;
-        return !strncmp(e, "rows", 4) ? atoi(e + 4) : 0;
-    }();
-    if (rows == 4 || rows == 8 || rows == 16) {
-        const long lanes = (long)B * ((H / 2 + rows - 1) / rows) * (W / 2) * (CP / 4);
-        if (rows == 4) wino_input_transform_rows<4><<<transform_blocks(lanes), 256, 0, s>>>(x, scale, V, B, H, W, C, CP, ntiles_pad);
-        else if (rows == 8) wino_input_transform_rows<8><<<transform_blocks(lanes), 256, 0, s>>>(x, scale, V, B, H, W, C, CP, ntiles_pad);
-        else wino_input_transform_rows<16><<<transform_blocks(lanes), 256, 0, s>>>(x, scale, V, B, H, W, C, CP, ntiles_pad);
+    const route::XformRoute t = route::input_transform_route(B, H, W, C, wino_knobs());
+    if (t.kernel == route::XFORM_ROWS) {
+        if (t.rows == 4) wino_input_transform_rows<4><<<t.blocks, route::XFORM_THREADS, 0, s>>>(x, scale, V, B, H, W, C, t.CP, t.ntiles_pad);
+        else if (t.rows == 8) wino_input_transform_rows<8><<<t.blocks, route::XFORM_THREADS, 0, s>>>(x, scale, V, B, H, W, C, t.CP, t.ntiles_pad);
+        else wino_input_transform_rows<16><<<t.blocks, route::XFORM_THREADS, 0, s>>>(x, scale, V, B, H, W, C, t.CP, t.ntiles_pad);
         return check_launch("winograd_input_transform(rows)");
     }
-    wino_input_transform<<<transform_blocks(ntiles * (CP / 4)), 256, 0, s>>>(x, scale, V, B, H, W, C, CP, ntiles_pad);
+    wino_input_transform<<<t.blocks, route::XFORM_THREADS, 0, s>>>(x, scale, V, B, H, W, C, t.CP, t.ntiles_pad);
     return check_launch("winograd_input_transform");
 }
 
 int winograd_gy_transform(const float* gy, const float* scale, float* Mg, int B, int H, int W, int C, hipStream_t s) {
-    const long ntiles = (long)B * (H / 2) * (W / 2);
-    long ntiles_pad;
-    int CP;
-    winograd_padded_dims(ntiles, C, &ntiles_pad, &CP);
-    wino_gy_transform<<<transform_blocks(ntiles * (CP / 4)), 256, 0, s>>>(gy, scale, Mg, B, H, W, C, CP, ntiles_pad);
+    const route::XformRoute t = route::gy_transform_route(B, H, W, C);
+    wino_gy_transform<<<t.blocks, route::XFORM_THREADS, 0, s>>>(gy, scale, Mg, B, H, W, C, t.CP, t.ntiles_pad);
     return check_launch("winograd_gy_transform");
 }
 
 }  // namespace gif
-
-extern "C" {
-
-// RP / CP of the transformed weight U [16][RP][CP] for `cout` / `cin` channels
-int gif_winograd_pack_dims(int cout, int cin, int* RP, int* CP) {
-    GIF_REQUIRE(cout > 0 && cin > 0 && RP && CP, "winograd_pack_dims: bad arguments");
-    *RP = (cout + WBN - 1) / WBN * WBN;
-    *CP = (cin + WBK - 1) / WBK * WBK;
-    return 0;
-}
-
-// floats of the V scratch of gif_conv3x3_winograd_f32: 16 planes x (tiles padded to the GEMM's M block) x padded channels
-int64_t gif_winograd_workspace_floats(int B, int H, int W, int C) {
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
-    const int64_t ntiles = (int64_t)B * (H / 2) * (W / 2);
-    const int64_t ntiles_pad = (ntiles + WPAD - 1) / WPAD * WPAD;
-    const int64_t CP = (C + WBK - 1) / WBK * WBK;
-    return 16 * ntiles_pad * CP;
-}
-
-int gif_winograd_weight_f32(const float* w, float* U, int R, int C, int RP, int CP, int64_t sr, int64_t sc, int64_t sky,
-                            int64_t skx, int flip, float scale, gif_stream_t stream) {
-    GIF_REQUIRE(w && U && R > 0 && C > 0 && RP >= R && CP >= C, "winograd_weight: bad arguments");
-    long total = (long)RP * CP;
-    wino_weight_transform<<<gif::cdiv(total, 256), 256, 0, gif::as_stream(stream)>>>(w, U, R, C, RP, CP, sr, sc, sky, skx,
-                                                                                      flip, scale);
-    return gif::check_launch("winograd_weight");
-}
-
-}  // extern "C"
 
 namespace {
 
@@ -1271,10 +1228,6 @@ namespace {
 struct WinoSums {
     float *colsum = nullptr, *dot = nullptr, *tmp = nullptr;
     int begin(WinoParams& p, const gif_conv_epilogue* e, int B, int H, int W, int Co, int bm, const char* who) {
-        p.mask_src = e ? static_cast<const float*>(e->mask_src) : nullptr;
-        p.mask_slope = e ? e->mask_slope : 1.f;
-        p.mask_gain = e ? e->mask_gain : 1.f;
-        p.dot_src = e ? static_cast<const float*>(e->dot_src) : nullptr;
         if (!e || (!e->colsum && !e->dot)) return 0;
         GIF_REQUIRE(e->red_ws, "%s: colsum / dot need the red_ws workspace (gif_conv_epilogue_ws_floats)", who);
         const long per_sample = (long)(H / 2) * (W / 2);
@@ -1301,69 +1254,148 @@ struct WinoSums {
     }
 };
 
-}  // namespace
-
-extern "C" {
-
-// y [B,H,W,Co] = act(out_scale * conv3x3_s1_p1(in_scale * x [B,H,W,C], weights behind U) + residual + bias).
-// V is scratch of gif_winograd_workspace_floats(B,H,W,C) floats.  H, W even; C, Co multiples of 4.
-int gif_conv3x3_winograd_f32(const float* x, const float* U, float* y, float* V, int B, int H, int W, int C, int Co,
-                             const gif_conv_epilogue* e, gif_stream_t stream) {
-    GIF_REQUIRE(x && U && y && V && B >= 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "winograd: bad dims (H, W must be even)");
-    GIF_REQUIRE(C > 0 && Co > 0 && C % 4 == 0 && Co % 4 == 0, "winograd: channels must be multiples of 4");
-    if (B == 0) return 0;
-    const long ntiles = (long)B * (H / 2) * (W / 2);
-    WinoParams p{};
-    gif_winograd_pack_dims(Co, C, &p.RP, &p.CP);
-    const long ntiles_pad = (ntiles + WPAD - 1) / WPAD * WPAD;
-    GIF_REQUIRE(ntiles_pad * p.CP < (1L << 31) && (long)B * H * W * Co < (1L << 31) && (long)B * H * W * C < (1L << 31),
-                "winograd: tensor too large for 32-bit offsets");
-    hipStream_t s = gif::as_stream(stream);
-    double flops = 2.0 * B * H * W * 9.0 * C * Co;  // ALGORITHMIC (direct-convolution) FLOPs
-    {
-        // x read once + V written once (the 4 overlapping patch reads of a pixel hit in L2)
-        gif::ProfScope prof_t(4, 4.0 * ((double)B * H * W * C + 16.0 * ntiles_pad * p.CP), s, (int)((long)B * H * W), C, 0, 1);
-        if (int rc = gif::winograd_input_transform(x, e ? e->in_scale : nullptr, V, B, H, W, C, s)) return rc;
-    }
-    gif::ProfScope prof(2, flops, s, (int)((long)B * H * W), Co, C, 1091);
-    p.V = V; p.U = U; p.y = y;
+// everything of WinoParams that comes from the epilogue
+void fill_epilogue(WinoParams& p, const gif_conv_epilogue* e) {
     p.out_scale = e ? e->out_scale : nullptr;
     p.bias = e ? e->bias : nullptr;
     p.residual = e ? static_cast<const float*>(e->residual) : nullptr;
     p.act = e ? e->act : 0;
     p.slope = e ? e->slope : 0.f;
     p.gain = e ? e->gain : 1.f;
-    p.B = B; p.H = H; p.W = W; p.Co = Co;
-    p.ntiles = (int)ntiles; p.ntiles_pad = (int)ntiles_pad; p.TH = H / 2; p.TW = W / 2;
-    p.tiles_m = (int)(ntiles_pad / WBM);
-    // 128-wide N tile (8 waves) whenever the output channels fill it; GIF_WINO_WN=2 / 4 forces a variant (benchmarking)
-    static int force_wn = -1;
-    if (force_wn < 0) {
-        const char* env = gif::knob("GIF_WINO_WN");
-        force_wn = env ? atoi(env) : 0;
-    }
-    // measured: +1-2 % on the >= 32^2 layers, slower when the launch has fewer than ~512 workgroups of 512 threads
-    const bool wide = force_wn == 4 ? (p.RP % 128 == 0)
-                                    : (force_wn == 2 ? false : (Co % 128 == 0 && (long)p.tiles_m * (p.RP / 128) >= 512));
-    const int bn = wide ? 128 : 64;
-    p.tiles_n = p.RP / bn;
-    WinoSums sums;
-    if (int rc = sums.begin(p, e, B, H, W, Co, WBM, "conv3x3_winograd")) return rc;
-    const size_t lds = (size_t)WNSTAGE * (WBM + bn) * WBK * sizeof(float);
-    static gif::LdsAttr attr2, attr4;
-    if (wide) attr4.ensure(reinterpret_cast<const void*>(wino_gemm_mfma<4>), lds);
-    else attr2.ensure(reinterpret_cast<const void*>(wino_gemm_mfma<2>), lds);
-    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
-    if (wide) hipLaunchKernelGGL(wino_gemm_mfma<4>, grid, dim3(512), lds, s, p);
-    else hipLaunchKernelGGL(wino_gemm_mfma<2>, grid, dim3(256), lds, s, p);
-    if (int rc = sums.finish(p, B, H, W, Co, WBM, s)) return rc;
-    return gif::check_launch("conv3x3_winograd");
+    p.mask_src = e ? static_cast<const float*>(e->mask_src) : nullptr;
+    p.mask_slope = e ? e->mask_slope : 1.f;
+    p.mask_gain = e ? e->mask_gain : 1.f;
+    p.dot_src = e ? static_cast<const float*>(e->dot_src) : nullptr;
 }
+
+// each launches its kernel iff `l` names exactly this instantiation
+template <int WN>
+bool mfma_try(const route::WinoLaunch& l, hipStream_t s, const WinoParams& p) {
+    if (l.kernel != route::GEMM_MFMA || l.WN != WN) return false;
+    static gif::LdsAttr attr;
+    auto kern = wino_gemm_mfma<WN>;
+    attr.ensure(reinterpret_cast<const void*>(kern), l.lds);
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), l.lds, s, p);
+    return true;
+}
+template <int BM, int BN>
+bool x3_try(const route::WinoLaunch& l, hipStream_t s, const WinoParams& p) {
+    if (l.kernel != route::GEMM_X3 || l.BM != BM || l.BN != BN) return false;
+    static gif::LdsAttr attr;
+    auto kern = wino_gemm_x3<BM, BN>;
+    attr.ensure(reinterpret_cast<const void*>(kern), l.lds);
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), l.lds, s, p);
+    return true;
+}
+template <int BM, int BN, int NST>
+bool h2_try(const route::WinoLaunch& l, hipStream_t s, const WinoParams& p) {
+    if (l.kernel != route::GEMM_H2 || l.BM != BM || l.BN != BN || l.NST != NST) return false;
+    static gif::LdsAttr attr;
+    auto kern = wino_gemm_h2<BM, BN, NST>;
+    attr.ensure(reinterpret_cast<const void*>(kern), l.lds);
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), l.lds, s, p);
+    return true;
+}
+
+// One GEMM launch of a route.  The ladder is the complete list of the Winograd GEMM instantiations the library carries (the kernels are
+// laid out in the code object in the ladder's order: reordering it moves them).
+int wino_launch_one(const route::WinoLaunch& l, hipStream_t s, const WinoParams& p, const char* who) {
+    const bool launched = mfma_try<4>(l, s, p) || mfma_try<2>(l, s, p) ||
+                          h2_try<128, 128, 3>(l, s, p) || h2_try<128, 128, 5>(l, s, p) || h2_try<128, 128, 4>(l, s, p) ||
+                          x3_try<256, 64>(l, s, p) || x3_try<128, 128>(l, s, p);
+    GIF_REQUIRE(launched, "%s: the route names a kernel that is not built (gemm %d wn %d tile %dx%d stages %d)", who, l.kernel, l.WN, l.BM, l.BN,
+                l.NST);
+    return 0;
+}
+
+// y [B,H,W,Co] = act(out_scale * conv3x3_s1_p1(in_scale * x [B,H,W,C], weights behind U) + residual + bias).
+// V is scratch of gif_winograd_workspace_floats(B,H,W,C) floats.  H, W even; C, Co multiples of 4.
+// mode (route::WinoMode) names the entry point.  U: the fp32 transform (native) or the bf16x3 one (split modes); U2: the f16x2 transform.
+// f16x2: the GEMM on U2 followed by its guarded bf16x3 twin on U (a no-op unless the gate was raised; U may be NULL: unguarded).
+int conv3x3_winograd_impl(int mode, const float* x, const void* U, const void* U2, float* y, float* V, int B, int H, int W, int C, int Co,
+                          const gif_conv_epilogue* e, gif_stream_t stream) {
+    const bool split = mode != route::MODE_NATIVE, h2 = mode == route::MODE_F16X2;
+    const char* const who = split ? "winograd_x3" : "winograd";
+    const char* const entry = split ? "conv3x3_winograd_f32x3" : "conv3x3_winograd";
+    GIF_REQUIRE(x && (U || U2) && y && V && B >= 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "%s: bad dims (H, W must be even)", who);
+    GIF_REQUIRE(C > 0 && Co > 0 && C % 4 == 0 && Co % 4 == 0, "%s: channels must be multiples of 4", who);
+    if (B == 0) return 0;
+    const route::WinoRoute r = route::wino_route(B, H, W, C, Co, mode, h2 && U, wino_knobs());
+    GIF_REQUIRE(r.error == route::WINO_OK, "%s: tensor too large for 32-bit offsets", who);
+    hipStream_t s = gif::as_stream(stream);
+    double flops = 2.0 * B * H * W * 9.0 * C * Co;  // ALGORITHMIC (direct-convolution) FLOPs
+    {
+        // x read once + V written once (the 4 overlapping patch reads of a pixel hit in L2)
+        gif::ProfScope prof_t(r.xform.family, 4.0 * ((double)B * H * W * C + 16.0 * r.ntiles_pad * r.CP), s, (int)((long)B * H * W), C, 0, 1);
+        if (int rc = gif::winograd_input_transform(x, e ? e->in_scale : nullptr, V, B, H, W, C, s)) return rc;
+    }
+    gif::ProfScope prof(r.family, flops, s, (int)((long)B * H * W), Co, C, split ? 2091 : 1091);
+    WinoParams p{};
+    p.V = V; p.U = static_cast<const float*>(U); p.y = y;
+    fill_epilogue(p, e);
+    p.B = B; p.H = H; p.W = W; p.Co = Co; p.RP = r.RP; p.CP = r.CP;
+    p.ntiles = (int)r.ntiles; p.ntiles_pad = (int)r.ntiles_pad; p.TH = H / 2; p.TW = W / 2;
+    p.tiles_m = r.primary.tiles_m; p.tiles_n = r.primary.tiles_n;
+    WinoSums sums;
+    if (int rc = sums.begin(p, e, B, H, W, Co, r.sum_tile, entry)) return rc;
+    if (h2) {
+        WinoParams q = p;
+        q.uexp = static_cast<const int*>(U2);
+        q.U = reinterpret_cast<const float*>(static_cast<const char*>(U2) + gif::h2_header_bytes(r.RP));
+        if (r.has_twin) {
+            const gif::H2Gate gt = gif::h2_next_gate(s);
+            if (gt.err) return gt.err;
+            q.gate = gt.word; q.gate_gen = gt.gen;
+        }
+        if (int rc = wino_launch_one(r.primary, s, q, entry)) return rc;
+        if (!q.gate) {  // unguarded
+            if (int rc = sums.finish(p, B, H, W, Co, r.sum_tile, s)) return rc;
+            return gif::check_launch("conv3x3_winograd_f32h2");
+        }
+        p.gate = q.gate; p.gate_gen = q.gate_gen; p.h2_stats = gif::h2_stats_words();
+        if (int rc = wino_launch_one(r.twin, s, p, entry)) return rc;
+    } else {
+        if (int rc = wino_launch_one(r.primary, s, p, entry)) return rc;
+    }
+    if (int rc = sums.finish(p, B, H, W, Co, r.sum_tile, s)) return rc;
+    return gif::check_launch(entry);
+}
+
+}  // namespace
+
+extern "C" {
+
+// RP / CP of the transformed weight U [16][RP][CP] for `cout` / `cin` channels
+int gif_winograd_pack_dims(int cout, int cin, int* RP, int* CP) {
+    GIF_REQUIRE(cout > 0 && cin > 0 && RP && CP, "winograd_pack_dims: bad arguments");
+    route::pack_dims(cout, cin, false, RP, CP);
+    return 0;
+}
+
+// floats of the V scratch of gif_conv3x3_winograd_f32: 16 planes x (tiles padded to the GEMM's M block) x padded channels
+int64_t gif_winograd_workspace_floats(int B, int H, int W, int C) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
+    return route::v_floats(B, H, W, C);
+}
+
+int gif_winograd_weight_f32(const float* w, float* U, int R, int C, int RP, int CP, int64_t sr, int64_t sc, int64_t sky,
+                            int64_t skx, int flip, float scale, gif_stream_t stream) {
+    GIF_REQUIRE(w && U && R > 0 && C > 0 && RP >= R && CP >= C, "winograd_weight: bad arguments");
+    long total = (long)RP * CP;
+    wino_weight_transform<<<gif::cdiv(total, 256), 256, 0, gif::as_stream(stream)>>>(w, U, R, C, RP, CP, sr, sc, sky, skx,
+                                                                                      flip, scale);
+    return gif::check_launch("winograd_weight");
+}
+
+int gif_conv3x3_winograd_f32(const float* x, const float* U, float* y, float* V, int B, int H, int W, int C, int Co,
+                             const gif_conv_epilogue* e, gif_stream_t stream) {
+    return conv3x3_winograd_impl(route::MODE_NATIVE, x, U, nullptr, y, V, B, H, W, C, Co, e, stream);
+}
+
 // ---- bf16x3 variants: same contract; U3 = [16][3][RP][CP] bf16 from gif_winograd_weight_f32x3, RP a multiple of 128
 int gif_winograd_pack_dims_x3(int cout, int cin, int* RP, int* CP) {
     GIF_REQUIRE(cout > 0 && cin > 0 && RP && CP, "winograd_pack_dims_x3: bad arguments");
-    *RP = (cout + 127) / 128 * 128;
-    *CP = (cin + WBK - 1) / WBK * WBK;
+    route::pack_dims(cout, cin, true, RP, CP);
     return 0;
 }
 
@@ -1376,103 +1408,16 @@ int gif_winograd_weight_f32x3(const float* w, void* U3, int R, int C, int RP, in
     return gif::check_launch("winograd_weight_f32x3");
 }
 
-}  // extern "C"
-
-// U2 != NULL: the f16x2 GEMM on U2 followed by its guarded bf16x3 twin on U3 (a no-op unless the gate was raised; U3 may be NULL: unguarded)
-static int conv3x3_winograd_x3_impl(const float* x, const void* U2, const void* U3, float* y, float* V, int B, int H, int W, int C, int Co,
-                                    const gif_conv_epilogue* e, gif_stream_t stream) {
-    GIF_REQUIRE(x && (U3 || U2) && y && V && B >= 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "winograd_x3: bad dims (H, W must be even)");
-    GIF_REQUIRE(C > 0 && Co > 0 && C % 4 == 0 && Co % 4 == 0, "winograd_x3: channels must be multiples of 4");
-    if (B == 0) return 0;
-    const long ntiles = (long)B * (H / 2) * (W / 2);
-    WinoParams p{};
-    gif_winograd_pack_dims_x3(Co, C, &p.RP, &p.CP);
-    const long ntiles_pad = (ntiles + WPAD - 1) / WPAD * WPAD;
-    GIF_REQUIRE(ntiles_pad * p.CP < (1L << 31) && (long)B * H * W * Co < (1L << 31) && (long)B * H * W * C < (1L << 31) &&
-                    3L * p.RP * p.CP < (1L << 31),
-                "winograd_x3: tensor too large for 32-bit offsets");
-    hipStream_t s = gif::as_stream(stream);
-    double flops = 2.0 * B * H * W * 9.0 * C * Co;  // ALGORITHMIC (direct-convolution) FLOPs
-    {
-        gif::ProfScope prof_t(4, 4.0 * ((double)B * H * W * C + 16.0 * ntiles_pad * p.CP), s, (int)((long)B * H * W), C, 0, 1);
-        if (int rc = gif::winograd_input_transform(x, e ? e->in_scale : nullptr, V, B, H, W, C, s)) return rc;
-    }
-    gif::ProfScope prof(U2 ? 14 : 10, flops, s, (int)((long)B * H * W), Co, C, 2091);
-    p.V = V; p.U = static_cast<const float*>(U3); p.y = y;
-    p.out_scale = e ? e->out_scale : nullptr;
-    p.bias = e ? e->bias : nullptr;
-    p.residual = e ? static_cast<const float*>(e->residual) : nullptr;
-    p.act = e ? e->act : 0;
-    p.slope = e ? e->slope : 0.f;
-    p.gain = e ? e->gain : 1.f;
-    p.B = B; p.H = H; p.W = W; p.Co = Co;
-    p.ntiles = (int)ntiles; p.ntiles_pad = (int)ntiles_pad; p.TH = H / 2; p.TW = W / 2;
-    // 128 x 128 blocks (4 x 2 waves) by default; GIF_WINO_X3_TILE=256 selects 256 x 64 (8 x 1 waves: every V fragment split
-    // once instead of twice) — measured equal (2.998 / 2.141 / 1.790 ms vs 2.993 / 2.133 / 1.757 ms on the three big layers)
-    static const int sq = gif::knob("GIF_WINO_X3_TILE") ? atoi(gif::knob("GIF_WINO_X3_TILE")) != 256 : 1;
-    const int bm = (sq || U2) ? 128 : 256, bn = (sq || U2) ? 128 : 64;
-    p.tiles_m = (int)(ntiles_pad / bm);
-    p.tiles_n = p.RP / bn;
-    WinoSums sums;
-    if (int rc = sums.begin(p, e, B, H, W, Co, bm, "conv3x3_winograd_f32x3")) return rc;
-    const size_t lds = (size_t)WNSTAGE * ((size_t)bm * WBK * sizeof(float) + 3 * (size_t)bn * 64);
-    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
-    if (U2) {
-        const int* hdr = static_cast<const int*>(U2);
-        WinoParams q = p;
-        q.uexp = hdr;
-        q.U = reinterpret_cast<const float*>(static_cast<const char*>(U2) + gif::h2_header_bytes(p.RP));
-        if (U3) {
-            const gif::H2Gate gt = gif::h2_next_gate(s);
-            if (gt.err) return gt.err;
-            q.gate = gt.word; q.gate_gen = gt.gen;
-        }
-        // ring depth 3 / 4 / 5 (96 / 128 / 160 KB): measured equal — 2.648 / 2.638 / 2.686 ms on 128 -> 128 at 256^2, batch 32: the GEMM does
-        // not wait for its DMA; GIF_WINO_H2_STAGES keeps the A/B
-        static const int nst = gif::knob("GIF_WINO_H2_STAGES") ? atoi(gif::knob("GIF_WINO_H2_STAGES")) : 3;
-        const size_t lds2 = (size_t)(nst == 3 ? 3 : nst == 5 ? 5 : 4) * ((size_t)128 * WBK * sizeof(float) + 2 * (size_t)128 * 64);
-        static gif::LdsAttr attr2[3];
-        if (nst == 3) {
-            attr2[0].ensure(reinterpret_cast<const void*>(wino_gemm_h2<128, 128, 3>), lds2);
-            hipLaunchKernelGGL((wino_gemm_h2<128, 128, 3>), grid, dim3(512), lds2, s, q);
-        } else if (nst == 5) {
-            attr2[2].ensure(reinterpret_cast<const void*>(wino_gemm_h2<128, 128, 5>), lds2);
-            hipLaunchKernelGGL((wino_gemm_h2<128, 128, 5>), grid, dim3(512), lds2, s, q);
-        } else {
-            attr2[1].ensure(reinterpret_cast<const void*>(wino_gemm_h2<128, 128, 4>), lds2);
-            hipLaunchKernelGGL((wino_gemm_h2<128, 128, 4>), grid, dim3(512), lds2, s, q);
-        }
-        if (!q.gate) {  // unguarded
-            if (int rc = sums.finish(p, B, H, W, Co, bm, s)) return rc;
-            return gif::check_launch("conv3x3_winograd_f32h2");
-        }
-        p.gate = q.gate; p.gate_gen = q.gate_gen; p.h2_stats = gif::h2_stats_words();
-    }
-#define GIF_WINO_X3_LAUNCH(BM_, BN_)                                                      \
-    {                                                                                     \
-        static gif::LdsAttr attr;                                                         \
-        attr.ensure(reinterpret_cast<const void*>(wino_gemm_x3<BM_, BN_>), lds);          \
-        hipLaunchKernelGGL((wino_gemm_x3<BM_, BN_>), grid, dim3(512), lds, s, p);         \
-    }
-    if (!sq && !U2) GIF_WINO_X3_LAUNCH(256, 64)
-    else GIF_WINO_X3_LAUNCH(128, 128)
-#undef GIF_WINO_X3_LAUNCH
-    if (int rc = sums.finish(p, B, H, W, Co, bm, s)) return rc;
-    return gif::check_launch("conv3x3_winograd_f32x3");
-}
-
-extern "C" {
-
 int gif_conv3x3_winograd_f32x3(const float* x, const void* U3, float* y, float* V, int B, int H, int W, int C, int Co,
                                const gif_conv_epilogue* e, gif_stream_t stream) {
-    return conv3x3_winograd_x3_impl(x, nullptr, U3, y, V, B, H, W, C, Co, e, stream);
+    return conv3x3_winograd_impl(route::MODE_BF16X3, x, U3, nullptr, y, V, B, H, W, C, Co, e, stream);
 }
 
 /* f16x2 (ABI 4): U2 from gif_winograd_weight_f32h2 (gif_winograd_weight_f32h2_bytes), U3 the bf16x3 transform of the same weights for
  * the guarded fallback (NULL: unguarded); same pack dims as the bf16x3 GEMM */
 int64_t gif_winograd_weight_f32h2_bytes(int RP, int CP) {
     if (RP <= 0 || CP <= 0) return 0;
-    return (int64_t)gif::h2_header_bytes(RP) + 16LL * 2 * RP * CP * 2;
+    return route::h2_weight_bytes(RP, CP);
 }
 
 /* U3 (optional): also write the bf16x3 transform of the same weights (gif_winograd_weight_f32x3's output) in the same launch */
@@ -1489,6 +1434,6 @@ int gif_winograd_weight_f32h2(const float* w, void* U2, void* U3, int R, int C, 
 int gif_conv3x3_winograd_f32h2(const float* x, const void* U2, const void* U3, float* y, float* V, int B, int H, int W, int C, int Co,
                                const gif_conv_epilogue* e, gif_stream_t stream) {
     GIF_REQUIRE(U2, "conv3x3_winograd_f32h2: null U2");
-    return conv3x3_winograd_x3_impl(x, U2, U3, y, V, B, H, W, C, Co, e, stream);
+    return conv3x3_winograd_impl(route::MODE_F16X2, x, U3, U2, y, V, B, H, W, C, Co, e, stream);
 }
 }

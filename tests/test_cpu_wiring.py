@@ -664,7 +664,7 @@ def test_pointwise_edges_fir_rows_match_the_oracle():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# tests/test_gpu_winograd_edges.py: the edge each row claims, recomputed from the constants of csrc/conv_winograd.hip and from
+# tests/test_gpu_winograd_edges.py: the edge each row claims, held against csrc/wino_route.h (through tests/host/wino_route_dump.cpp) and
 # csrc/wgrad_route.h (through tests/host/wgrad_route_dump.cpp), and its fp64 restatements tied to ATen float64.  No GPU.
 # ---------------------------------------------------------------------------------------------------------------------------------
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -676,30 +676,58 @@ def _winograd():
 
 
 def test_winograd_edges_constants_are_the_sources():
-    """A constant changed in conv_winograd.hip fails here; it does not silently move a row off its edge."""
+    """A constant or a decision changed in csrc/wino_route.h fails here; it does not silently move a row off its edge: K is the header's
+    constants, and geometry() — written from the host code before the header existed — is what the header reports (through
+    tests/host/wino_route_dump.cpp, a stand-alone program under ASan + UBSan) for every row in every mode."""
     import re
+    import subprocess
+    import tempfile
+    from gif_amd import ops
     WE = _winograd()
-    with open(os.path.join(ROOT, "gif_amd", "csrc", "conv_winograd.hip")) as f:
-        src = f.read()
-
-    def one(pattern):
-        m = re.findall(pattern, src)
-        assert len(m) == 1, (pattern, m)
-        return m[0]
-
-    wbm, wbn, wbk = map(int, one(r"constexpr int WBM = (\d+), WBN = (\d+), WBK = (\d+), WNSTAGE = 3;"))
-    a, b, c, d = map(int, one(r"if \(blocks > (\d+) \* (\d+)\) blocks = (\d+) \* (\d+);"))
-    assert (a, b) == (c, d)
-    got = dict(WBM=wbm, WBN=wbn, WBK=wbk, WPAD=int(one(r"constexpr int WPAD = (\d+);")), CAP_WG=a * b,
-               TYB=int(one(r"if \(!e\) return (\d+);\n\s+return !strncmp\(e, \"rows\", 4\)")),
-               WIDE_MIN=int(one(r"\(Co % 128 == 0 && \(long\)p\.tiles_m \* \(p\.RP / 128\) >= (\d+)\)")))
-    assert got == WE.K
-    # the expressions geometry() restates
-    one(r"const long lanes = \(long\)B \* \(\(H / 2 \+ rows - 1\) / rows\) \* \(W / 2\) \* \(CP / 4\);")
-    one(r"long blocks = \(total \+ 255\) / 256;")
-    one(r"p\.tiles_m = \(int\)\(ntiles_pad / WBM\);")
-    one(r"const int bm = \(sq \|\| U2\) \? 128 : 256, bn = \(sq \|\| U2\) \? 128 : 64;")
-    assert len(re.findall(r"for \(unsigned idx = blockIdx\.x \* blockDim\.x \+ threadIdx\.x; idx < [^;]+; idx \+= gridDim\.x \* blockDim\.x\)", src)) == 3
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    flags = "-x c++ -std=c++17 -O1 -g -Wall -Werror -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
+    cases, args = [], ["K"]
+    before = ops.get_fp32_mfma_mode()
+    try:
+        for row in WE.FROWS:
+            for mode in WE.MODES:  # (every mode, also those the GPU test of the row does not run)
+                ops.set_fp32_mfma_mode(mode)
+                entry = ops.winograd_mode("fwd", row.shape[2])  # the entry point ops.conv3x3_winograd calls
+                B, C, Co, H, W = row.shape
+                cases.append((row, mode, entry))
+                args += ["fwd"] + [str(v) for v in (B, H, W, C, Co, WE.MODES.index(entry), 1)]
+    finally:
+        ops.set_fp32_mfma_mode(before)
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "wino_route_dump")
+        built = subprocess.run([hipcc] + flags.split() + ["-I", os.path.join(ROOT, "gif_amd", "csrc"),
+                                                          os.path.join(ROOT, "tests", "host", "wino_route_dump.cpp"), "-o", exe],
+                               capture_output=True, text=True, timeout=600)
+        assert built.returncode == 0, built.stderr[-4000:]
+        ran = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300)
+    assert ran.returncode == 0, (ran.returncode, ran.stderr[-4000:])
+    lines = ran.stdout.splitlines()
+    assert len(lines) == len(cases) + 1
+    assert {k: int(v) for k, v in (f.split("=") for f in lines[0].split())} == dict(WE.K, WNSTAGE=3)
+    pat = re.compile(r"-> rows<8> lanes(\d+) blocks(\d+) thr256 trips(\d+) fam4 ; (mfma<2>|mfma<4>|x3<128,128>|h2<128,128,3>) bm(\d+) bn(\d+) tm(\d+) tn(\d+) "
+                     r"grid(\d+) thr(\d+) lds\d+(?: \+ twin x3<128,128> bm128 bn128 tm(\d+) tn(\d+) grid(\d+) thr512 lds\d+)? ; "
+                     r"ntiles(\d+) pad(\d+) RP(\d+) CP(\d+) ")
+    names = {"mfma<2>": "mfma2", "mfma<4>": "mfma4", "x3<128,128>": "x3", "h2<128,128,3>": "h2"}
+    seen = set()
+    for (row, mode, entry), l in zip(cases, lines[1:]):
+        geo = WE.geometry(*row.shape, mode)
+        m = pat.search(l)
+        assert m, l
+        lanes, blocks, trips, gemm, bm, bn, tm, tn, grid, thr = m.groups()[:10]
+        ntiles, pad, rp, cp = (int(v) for v in m.groups()[13:])
+        got = dict(ntiles=ntiles, ntiles_pad=pad, CP=cp, RP=rp, tiles_m=int(tm), tiles_n=int(tn), nwg=int(grid), wide=gemm == "mfma<4>",
+                   gemm=names[gemm], lanes=int(lanes), trips=int(trips))
+        assert got == {k: geo[k] for k in got}, (row.name, mode, l)
+        assert (int(bm), int(bn)) == (geo["ntiles_pad"] // geo["tiles_m"], geo["RP"] // geo["tiles_n"]), (row.name, mode, l)
+        assert int(blocks) == min(-(-geo["lanes"] // 256), WE.K["CAP_WG"]) and int(thr) == (256 if gemm == "mfma<2>" else 512), (row.name, mode, l)
+        assert (entry == "f16x2") == (m.group(11) is not None) and (m.group(11) is None or m.groups()[10:13] == (tm, tn, grid)), (row.name, mode, l)
+        seen.add(got["gemm"])
+    assert seen == {"mfma2", "mfma4", "x3", "h2"}
     assert WE.CAP_LANES == 2097152 == 32 * 16 * 128 * 32  # the benchmark's own shape: batch 32, 256^2, 128 channels
 
 

@@ -41,7 +41,9 @@ sentinels behind the size the library asks for, pre-filled with zeros, quiet NaN
 group 2^-24 below the others: results bit-equal between the fills, finite, sentinels untouched, and the f16x2 gate unmoved — against
 weights whose packed rows carry the narrow flag, with a control that puts the same group into a real row of x.
 
-Out of scope: the knob-only A/B kernels (GIF_WINO_XFORM, GIF_WINO_WN, GIF_WINO_X3_TILE, GIF_WINO_H2_STAGES are read once per process).
+Out of scope: RUNNING the knob-only A/B kernels (GIF_WINO_XFORM, GIF_WINO_WN, GIF_WINO_X3_TILE, GIF_WINO_H2_STAGES are read once per
+process).  Which kernel, tile and ring depth each value of the four selects is covered on the CPU: csrc/wino_route.h parses them, and
+tests/golden/wino_route_table.txt (tests/test_wino_route.py) records the route of every value.
 """
 import ctypes
 import math
@@ -63,7 +65,7 @@ SQRT2 = 2 ** 0.5
 TOL.update({"wino_v": 5 * 2.0 ** -24})
 TINY.update({"wino_v": 1e-30})
 
-# The constants of csrc/conv_winograd.hip this module's rows are computed from (tests/test_cpu_wiring.py reads them back from the source)
+# The constants of csrc/wino_route.h this module's rows are computed from (tests/test_cpu_wiring.py holds them to the header's)
 K = dict(WBM=128, WBN=64, WBK=32, WPAD=256, TYB=8, CAP_WG=256 * 32, WIDE_MIN=512)
 CAP_LANES = K["CAP_WG"] * 256  # 2 097 152 lanes per trip of the transforms' grid-stride loop
 
