@@ -212,3 +212,45 @@ def check(rc, what):
     if rc != 0:
         msg = load().gif_last_error().decode(errors="replace")
         raise GifHipError(f"{what} failed (rc={rc}): {msg}")
+
+
+def marshal(entry, args):
+    """What ctypes receives for `args` of entry point `entry`: a tensor gives its address, everything else (None, numbers, ctypes
+    objects, an address the caller took itself) goes through as it is.  The kernels index dense arrays, so a non-contiguous tensor
+    is refused.  Pure host code: touches neither the library nor a device."""
+    out = list(args)
+    for i, a in enumerate(out):
+        if isinstance(a, torch.Tensor):
+            if not a.is_contiguous():
+                raise GifHipError(f"{entry}: argument {i} is not contiguous (shape {list(a.shape)}, strides {list(a.stride())})")
+            out[i] = a.data_ptr()
+    return out
+
+
+def launch(entry, device, *args):
+    """entry(*args, stream) with `device` current and `stream` its current stream (read inside the guard: a stream read before it
+    would be another device's); `args` as `marshal` takes them; the return code is checked under the entry's name.  One process
+    per GPU never enters a device context."""
+    fn, argv = getattr(load(), entry), marshal(entry, args)
+    if device.index in (None, torch.cuda.current_device()):
+        return check(fn(*argv, torch.cuda.current_stream().cuda_stream), entry)
+    with torch.cuda.device(device):
+        check(fn(*argv, torch.cuda.current_stream().cuda_stream), entry)
+
+
+def workspace(nbytes, device):
+    """fp32 scratch of at least `nbytes` bytes and at least one element (a gif_*_workspace_bytes figure) on `device`"""
+    return torch.empty((max(nbytes // 4, 1),), device=device, dtype=torch.float32)
+
+
+def require_device(what, **tensors):
+    """The public entry points' refusal: every named argument that is given (not None) is a tensor on one GPU."""
+    first = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GifHipError(f"{what} needs device tensors (no CPU fallback): {name}")
+        first = first or (name, t.device)
+        if t.device != first[1]:
+            raise GifHipError(f"{what}: {name} is on {t.device}, {first[0]} on {first[1]}")

@@ -68,30 +68,18 @@ def _check_hops(max_hops, what):
     return int(max_hops)
 
 
-def _one_topology(faces, B, what):
-    if faces.ndimension() == 3 and B > 1 and faces.stride(0) != 0 and not torch.equal(faces, faces[:1].expand_as(faces)):
-        raise _lib.GifHipError(f"{what} needs one face topology for the whole batch")
-
-
 class _AntialiasFn(Function):
     @staticmethod
     def forward(ctx, image, vertices_ndc, tri, depth, faces, max_hops):
         B, C, h, w = image.shape
-        _one_topology(faces, B, "antialias")
-        faces_b = faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
-        fv = sr.face_vertices(sr.to_image_space(vertices_ndc.float(), h, w), faces_b)
-        F = fv.shape[1]
+        render._one_topology(faces, B, "antialias")
+        fv = render._projected_face_vertices(vertices_ndc, faces, h, w)
         adj = edge_adjacency(faces)
         img = image.float().contiguous()
         tri, depth = tri.contiguous(), depth.float().contiguous()
         out = torch.empty_like(img)
-        with torch.cuda.device(img.device):  # launch on the operands' device and its current stream
-            args = (img.data_ptr(), tri.data_ptr(), depth.data_ptr(), fv.data_ptr(), adj.data_ptr(), out.data_ptr(), B, C, F, h, w)
-            stream = torch.cuda.current_stream().cuda_stream
-            if max_hops == 0:
-                _lib.check(_lib.load().gif_antialias_f32(*args, stream), "antialias")
-            else:
-                _lib.check(_lib.load().gif_antialias_walk_f32(*args, max_hops, stream), "antialias_walk")
+        walk = ("gif_antialias_walk_f32", max_hops) if max_hops else ("gif_antialias_f32",)
+        _lib.launch(walk[0], img.device, img, tri, depth, fv, adj, out, B, C, fv.shape[1], h, w, *walk[1:])
         ctx.save_for_backward(img, tri, depth, fv, adj)
         ctx.faces, ctx.V, ctx.max_hops = faces, vertices_ndc.shape[1], max_hops
         ctx.dtypes = (image.dtype, vertices_ndc.dtype)
@@ -103,34 +91,16 @@ class _AntialiasFn(Function):
         img, tri, depth, fv, adj = ctx.saved_tensors
         B, C, h, w = img.shape
         F = fv.shape[1]
-        need_i, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_i, need_v = ctx.needs_input_grad[:2]
         if not (need_i or need_v):
             return None, None, None, None, None, None
-        dev = img.device
-        lib = _lib.load()
-        g = gout.float().contiguous()
         gi = torch.empty_like(img) if need_i else None
         gfv = torch.empty_like(fv) if need_v else None
-        ws = torch.empty((max(lib.gif_antialias_bwd_workspace_bytes(B, F, h, w) // 4, 1) if need_v else 1,), device=dev,
-                         dtype=torch.float32)
-        gv = None
-        with torch.cuda.device(dev):
-            args = (img.data_ptr(), tri.data_ptr(), depth.data_ptr(), fv.data_ptr(), adj.data_ptr(), g.data_ptr(),
-                    gi.data_ptr() if need_i else None, gfv.data_ptr() if need_v else None, B, C, F, h, w)
-            stream = torch.cuda.current_stream().cuda_stream
-            if ctx.max_hops == 0:
-                _lib.check(lib.gif_antialias_bwd_f32(*args, ws.data_ptr(), stream), "antialias_bwd")
-            else:
-                _lib.check(lib.gif_antialias_walk_bwd_f32(*args, ctx.max_hops, ws.data_ptr(), stream), "antialias_walk_bwd")
-            if need_v:
-                if F == 0:
-                    gv = torch.zeros((B, ctx.V, 3), device=dev, dtype=ctx.dtypes[1])
-                else:
-                    _, off, ent = render._topology(ctx.faces, ctx.V, dev)
-                    gv = render._face_gather_bwd(gfv, off, ent, ctx.V)
-                    # to_image_space: x * w/2 + w/2, y * h/2 + h/2; z only orders the faces (no gradient)
-                    gv *= torch.tensor([w / 2, h / 2, 0.0], device=dev, dtype=torch.float32)
-                    gv = gv.to(ctx.dtypes[1])
+        # (the workspace serves the vertex gradient alone: one element without it)
+        ws = _lib.workspace(_lib.load().gif_antialias_bwd_workspace_bytes(B, F, h, w) if need_v else 0, img.device)
+        walk = ("gif_antialias_walk_bwd_f32", ctx.max_hops) if ctx.max_hops else ("gif_antialias_bwd_f32",)
+        _lib.launch(walk[0], img.device, img, tri, depth, fv, adj, gout.float().contiguous(), gi, gfv, B, C, F, h, w, *walk[1:], ws)
+        gv = render._ndc_vertex_grad(gfv, ctx.faces, ctx.V, h, w, ctx.dtypes[1]) if need_v else None
         return (gi.to(ctx.dtypes[0]) if need_i else None), gv, None, None, None, None
 
 
@@ -141,9 +111,7 @@ def antialias(image, tri, depth, vertices_ndc, faces, max_hops=0):
     vertices_ndc; not twice.  max_hops (0 .. 64) > 0: a pair whose front face does not own the outline edge walks on across up to
     that many non-silhouette edges to the face that does; 0 is §3o's definition and its kernels."""
     max_hops = _check_hops(max_hops, "antialias")
-    for name, t in (("image", image), ("tri", tri), ("depth", depth), ("vertices_ndc", vertices_ndc), ("faces", faces)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.GifHipError(f"antialias needs device tensors (no CPU fallback): {name}")
+    _lib.require_device("antialias", image=image, tri=tri, depth=depth, vertices_ndc=vertices_ndc, faces=faces)
     if image.ndimension() != 4 or image.shape[1] < 1 or tri.shape != (image.shape[0],) + image.shape[2:] or tri.shape != depth.shape:
         raise _lib.GifHipError("antialias: image [B,C,h,w] with C >= 1, tri and depth [B,h,w]")
     if tri.dtype != torch.int32:
@@ -153,45 +121,14 @@ def antialias(image, tri, depth, vertices_ndc, faces, max_hops=0):
     return _AntialiasFn.apply(image, vertices_ndc, tri, depth, faces, max_hops)
 
 
-class _RasterizeBuffersFn(Function):
-    """render._RasterizeAttributesFn's launches and backward, handing the face-index and depth buffers back as well."""
-
-    @staticmethod
-    def forward(ctx, vertices_ndc, attributes, faces, h, w):
-        fv, fc, tri, img, mask, depth = render._rasterize_colors(
-            vertices_ndc, faces, lambda faces_b: sr.face_vertices(attributes.float().contiguous(), faces_b), h, w, with_depth=True)
-        ctx.mark_non_differentiable(mask, tri, depth)
-        ctx.save_for_backward(fv, fc, tri)
-        ctx.faces, ctx.hw = faces, (h, w)
-        ctx.dtypes = (vertices_ndc.dtype, attributes.dtype)
-        ctx.V = (vertices_ndc.shape[1], attributes.shape[1])
-        return img, mask, tri, depth
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gimg, _gmask, _gtri, _gdepth):
-        fv, fc, tri = ctx.saved_tensors
-        faces, (h, w) = ctx.faces, ctx.hw
-        need_v, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gv, gfc = render._rasterize_colors_bwd(fv, fc, tri, gimg, faces, ctx.V[0], ctx.dtypes[0], h, w, need_v, need_a,
-                                               "rasterize_attributes_aa")
-        ga = None
-        if need_a:
-            with torch.cuda.device(fv.device):
-                _, off, ent = render._topology(faces, ctx.V[1], fv.device)
-                ga = render._face_gather_bwd(gfc, off, ent, ctx.V[1]).to(ctx.dtypes[1])
-        return gv, ga, None, None, None
-
-
 def rasterize_attributes_aa(vertices_ndc, faces, attributes, h, w, max_hops=0):
     """render.rasterize_attributes with an antialiased outline: (image_aa [B,3,h,w], coverage_aa [B,1,h,w]).  The rasteriser's
     launches, then `antialias` over the three attribute channels and the 0 / 1 mask as a fourth.  Both outputs are differentiable:
     inside the faces as rasterize_attributes is, and at silhouette edges through the blend — a loss on coverage_aa alone reaches
     the vertices.  max_hops: as in `antialias`."""
     max_hops = _check_hops(max_hops, "rasterize_attributes_aa")
-    if not vertices_ndc.is_cuda:
-        raise _lib.GifHipError("rasterize_attributes_aa needs device tensors (no CPU fallback)")
-    img, mask, tri, depth = _RasterizeBuffersFn.apply(vertices_ndc, attributes, faces, h, w)
+    _lib.require_device("rasterize_attributes_aa", vertices_ndc=vertices_ndc)
+    img, mask, tri, depth = render._RasterizeColorsFn.apply(vertices_ndc, attributes, faces, h, w, True, "rasterize_attributes_aa")
     out = antialias(torch.cat((img, mask.to(img.dtype)), dim=1), tri, depth, vertices_ndc, faces, max_hops)
     return out[:, :3], out[:, 3:]
 
@@ -200,13 +137,12 @@ def soft_silhouette(vertices_ndc, faces, h, w, max_hops=0):
     """coverage_aa [B,1,h,w] alone: one rasteriser pass for the face-index and depth buffers (no attribute gather), then `antialias`
     over the 0 / 1 mask.  Differentiable with respect to x, y of vertices_ndc.  max_hops: as in `antialias`."""
     max_hops = _check_hops(max_hops, "soft_silhouette")
-    if not vertices_ndc.is_cuda:
-        raise _lib.GifHipError("soft_silhouette needs device tensors (no CPU fallback)")
+    _lib.require_device("soft_silhouette", vertices_ndc=vertices_ndc)
     B = vertices_ndc.shape[0]
     with torch.no_grad():
-        faces_b = faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
-        fv = sr.face_vertices(sr.to_image_space(vertices_ndc.float(), h, w), faces_b)
+        fv = render._projected_face_vertices(vertices_ndc, faces, h, w)
         depth, tri, bary = sr.new_buffers(B, h, w, vertices_ndc.device)
         sr.standard_rasterize(fv, depth, tri, bary, h, w)
         mask = (tri >= 0)[:, None].float()
     return antialias(mask, tri, depth, vertices_ndc, faces, max_hops)
+

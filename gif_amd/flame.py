@@ -277,10 +277,7 @@ class _FlameSkinFn(Function):
         keep = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         verts = torch.empty((B, V, 3), device=coef.device, dtype=torch.float32)
         v_posed = torch.empty_like(verts) if keep else None
-        with torch.cuda.device(coef.device):  # launch on the operands' device and its current stream
-            _lib.check(_lib.load().gif_flame_skin_f32(tmpl.data_ptr(), dirs.data_ptr(), lbs_w.data_ptr(), coef.data_ptr(),
-                                                      A.data_ptr(), verts.data_ptr(), v_posed.data_ptr() if keep else None,
-                                                      B, V, KP, J, torch.cuda.current_stream().cuda_stream), "flame_skin")
+        _lib.launch("gif_flame_skin_f32", coef.device, tmpl, dirs, lbs_w, coef, A, verts, v_posed, B, V, KP, J)
         if keep:
             ctx.save_for_backward(A, v_posed, dirs, lbs_w)
         ctx.dtypes = (coef.dtype, A.dtype)
@@ -294,26 +291,17 @@ class _FlameSkinFn(Function):
         KP, J = dirs.shape[0], lbs_w.shape[1]
         need_c, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g = g_verts.contiguous().float()
-        lib = _lib.load()
         dev = g.device
         g_coef = torch.empty((B, KP), device=dev, dtype=torch.float32) if need_c else None
         g_A = torch.empty((B, J, 12), device=dev, dtype=torch.float32) if need_a else None
-        ws = torch.empty((max(lib.gif_flame_skin_bwd_workspace_bytes(B, V, KP, J) // 4, 1),), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.check(lib.gif_flame_skin_bwd_f32(dirs.data_ptr(), lbs_w.data_ptr(), A.data_ptr(), g.data_ptr(), v_posed.data_ptr(),
-                                                  g_coef.data_ptr() if need_c else None, g_A.data_ptr() if need_a else None,
-                                                  B, V, KP, J, ws.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                       "flame_skin_bwd")
+        ws = _lib.workspace(_lib.load().gif_flame_skin_bwd_workspace_bytes(B, V, KP, J), dev)
+        _lib.launch("gif_flame_skin_bwd_f32", dev, dirs, lbs_w, A, g, v_posed, g_coef, g_A, B, V, KP, J, ws)
         return g_coef, g_A, None, None, None
 
 
 def _launch_landmarks_bwd(g_lmk, row, tables, g_verts, B, V, R, Ld, Ls):
     """The one place gif_flame_landmarks_bwd_f32 is launched from (on g_verts' device and its current stream)."""
-    ptr = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(g_verts.device):
-        _lib.check(_lib.load().gif_flame_landmarks_bwd_f32(g_lmk.data_ptr(), ptr(row), *[ptr(t) for t in tables], g_verts.data_ptr(),
-                                                           B, V, R, Ld, Ls, torch.cuda.current_stream().cuda_stream),
-                   "flame_landmarks_bwd")
+    _lib.launch("gif_flame_landmarks_bwd_f32", g_verts.device, g_lmk, row, *tables, g_verts, B, V, R, Ld, Ls)
 
 
 class _FlameLandmarksFn(Function):
@@ -323,19 +311,14 @@ class _FlameLandmarksFn(Function):
 
     @staticmethod
     def forward(ctx, verts, A, yaw_joint, R, Ld, Ls, dyn_vid, dyn_bary, st_vid, st_bary):
-        if not (verts.is_cuda and A.is_cuda):
-            raise _lib.GifHipError("flame landmarks need device tensors (no CPU fallback)")
+        _lib.require_device("flame landmarks", verts=verts, A=A)
         B, V, _ = verts.shape
         J = A.shape[1]
         verts, A = verts.contiguous().float(), A.contiguous().float()
         tables = (dyn_vid, dyn_bary, st_vid, st_bary)
         lmk = torch.empty((B, Ld + Ls, 3), device=verts.device, dtype=torch.float32)
         row = torch.empty((B,), device=verts.device, dtype=torch.int32)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(verts.device):  # launch on the operands' device and its current stream
-            _lib.check(_lib.load().gif_flame_landmarks_f32(verts.data_ptr(), A.data_ptr(), *[ptr(t) for t in tables], lmk.data_ptr(),
-                                                           row.data_ptr(), B, V, J, yaw_joint, R, Ld, Ls,
-                                                           torch.cuda.current_stream().cuda_stream), "flame_landmarks")
+        _lib.launch("gif_flame_landmarks_f32", verts.device, verts, A, *tables, lmk, row, B, V, J, yaw_joint, R, Ld, Ls)
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(row, *[t for t in tables if t is not None])
             ctx.present = [t is not None for t in tables]
@@ -420,20 +403,14 @@ class FlameLayer(nn.Module):
         return self.lbs_weights.shape[0]
 
     def _rows(self, t, n, name, B):
-        if t is None:
-            return None
-        if not t.is_cuda:
-            raise _lib.GifHipError(f"FlameLayer needs device tensors ({name} is on the CPU; no CPU fallback)")
-        if t.ndimension() != 2 or t.shape != (B, n):
+        if t is not None and (t.ndimension() != 2 or t.shape != (B, n)):
             raise ValueError(f"{name} must be [{B},{n}], got {list(t.shape)}")
-        if t.device != self.dirs.device:
-            raise _lib.GifHipError(f"{name} is on {t.device}, the layer's constants on {self.dirs.device}")
         return t
 
     def forward(self, shape_params=None, expression_params=None, pose_params=None, neck_pose=None, eye_pose=None):
+        _lib.require_device("FlameLayer", layer=self.dirs, shape_params=shape_params, expression_params=expression_params,
+                            pose_params=pose_params, neck_pose=neck_pose, eye_pose=eye_pose)
         given = [t for t in (shape_params, expression_params, pose_params, neck_pose, eye_pose) if t is not None]
-        if not self.dirs.is_cuda or any(not t.is_cuda for t in given):
-            raise _lib.GifHipError("FlameLayer needs device tensors and a layer moved to the device (no CPU fallback)")
         B = given[0].shape[0] if given else 1
         ins = [self._rows(t, n, name, B) for t, n, name in (
             (shape_params, self.n_shape, "shape_params"), (expression_params, self.n_exp, "expression_params"),
@@ -448,28 +425,21 @@ class FlameLayer(nn.Module):
         dev = self.dirs.device
         V, J = self.lbs_weights.shape
         KP = self.dirs.shape[0]
-        args = []
-        for t in ins:  # (pointer, row stride): views such as flame_batch[:, 0:100] go in as they are
+        keep, args = [], []
+        for t in ins:  # (address, row stride): views such as flame_batch[:, 0:100] go in as they are, so as addresses
             if t is None:
                 args += [None, 0]
                 continue
             if t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
                 t = t.float().contiguous()
-            args += [t, t.stride(0)]
-        ptr = lambda t: None if t is None else t.data_ptr()
+            keep.append(t)  # (alive until both launches are queued)
+            args += [t.data_ptr(), t.stride(0)]
         coef = torch.empty((B, KP), device=dev, dtype=torch.float32)
         A = torch.empty((B, J, 12), device=dev, dtype=torch.float32)
         verts = torch.empty((B, V, 3), device=dev, dtype=torch.float32)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(lib.gif_flame_joints_f32(self.J0.data_ptr(), self.Jdirs.data_ptr(), self._parents_c,
-                                                ptr(args[0]), args[1], self.n_shape, ptr(args[2]), args[3], self.n_exp,
-                                                ptr(args[4]), args[5], ptr(args[6]), args[7], ptr(args[8]), args[9],
-                                                A.data_ptr(), coef.data_ptr(), B, KP, J, stream), "flame_joints")
-            _lib.check(lib.gif_flame_skin_f32(self.v_template.data_ptr(), self.dirs.data_ptr(), self.lbs_weights.data_ptr(),
-                                              coef.data_ptr(), A.data_ptr(), verts.data_ptr(), None, B, V, KP, J, stream),
-                       "flame_skin")
+        _lib.launch("gif_flame_joints_f32", dev, self.J0, self.Jdirs, self._parents_c, *args[0:2], self.n_shape, *args[2:4],
+                    self.n_exp, *args[4:], A, coef, B, KP, J)
+        _lib.launch("gif_flame_skin_f32", dev, self.v_template, self.dirs, self.lbs_weights, coef, A, verts, None, B, V, KP, J)
         return verts, A
 
     def _forward_grad(self, B, shape, exp, pose, neck, eye):

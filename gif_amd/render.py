@@ -58,13 +58,38 @@ def _topology(faces, V, device):
 
 
 def _face_gather_bwd(gface, off, ent, V):
-    """d face_vertices(x, faces) [B,F,3,3] -> d x [B,V,3]: per-vertex gather over the CSR (deterministic, no atomics)."""
+    """d face_vertices(x, faces) [B,F,3,3] -> d x [B,V,3]: per-vertex gather over the CSR (deterministic, no atomics); no face, no
+    launch: exact zeros."""
     B, F = gface.shape[:2]
-    gface = gface.contiguous()
+    if F == 0:
+        return torch.zeros((B, V, 3), device=gface.device, dtype=torch.float32)
     out = torch.empty((B, V, 3), device=gface.device, dtype=torch.float32)
-    _lib.check(_lib.load().gif_face_gather_bwd_f32(gface.data_ptr(), off.data_ptr(), ent.data_ptr(), out.data_ptr(), B, V, F,
-                                                    torch.cuda.current_stream().cuda_stream), "face_gather_bwd")
+    _lib.launch("gif_face_gather_bwd_f32", gface.device, gface.contiguous(), off, ent, out, B, V, F)
     return out
+
+
+def _batched_faces(faces, B):
+    """faces [F,3] (a view, no copy) or [B,F,3] -> [B,F,3]"""
+    return faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
+
+
+def _projected_face_vertices(vertices_ndc, faces, h, w):
+    """pixel-space face vertices [B,F,3,3] float32 of vertices_ndc [B,V,3]: what every rasteriser and antialias launch reads"""
+    return sr.face_vertices(sr.to_image_space(vertices_ndc.float(), h, w), _batched_faces(faces, vertices_ndc.shape[0]))
+
+
+def _one_topology(faces, B, what):
+    if faces.ndimension() == 3 and B > 1 and faces.stride(0) != 0 and not torch.equal(faces, faces[:1].expand_as(faces)):
+        raise _lib.GifHipError(f"{what} needs one face topology for the whole batch")
+
+
+def _ndc_vertex_grad(gfv, faces, V, h, w, dtype):
+    """d pixel-space face vertices [B,F,3,3] -> d vertices_ndc [B,V,3] in `dtype`: the face gather's transpose, then to_image_space's
+    x * w/2 + w/2, y * h/2 + h/2; z only orders the faces (no gradient)."""
+    _, off, ent = _topology(faces, V, gfv.device)
+    gv = _face_gather_bwd(gfv, off, ent, V)
+    gv *= torch.tensor([w / 2, h / 2, 0.0], device=gfv.device, dtype=torch.float32)
+    return gv.to(dtype)
 
 
 class _VertexNormalsFn(Function):
@@ -73,11 +98,7 @@ class _VertexNormalsFn(Function):
         B, V, _ = vertices.shape
         verts = vertices.contiguous().float()
         out = torch.empty_like(verts)
-        lib = _lib.load()
-        with torch.cuda.device(verts.device):  # launch on the operands' device and its current stream
-            _lib.check(lib.gif_vertex_normals_f32(verts.data_ptr(), f32.data_ptr(), off.data_ptr(), ent.data_ptr(),
-                                                  out.data_ptr(), B, V, f32.shape[0],
-                                                  torch.cuda.current_stream().cuda_stream), "vertex_normals")
+        _lib.launch("gif_vertex_normals_f32", verts.device, verts, f32, off, ent, out, B, V, f32.shape[0])
         ctx.save_for_backward(verts, f32, off, ent)
         ctx.in_dtype = vertices.dtype
         return out
@@ -87,14 +108,10 @@ class _VertexNormalsFn(Function):
     def backward(ctx, gout):
         verts, f32, off, ent = ctx.saved_tensors
         B, V, _ = verts.shape
-        gout = gout.contiguous().float()
         work = torch.empty_like(verts)
         gv = torch.empty_like(verts)
-        with torch.cuda.device(verts.device):
-            _lib.check(_lib.load().gif_vertex_normals_bwd_f32(verts.data_ptr(), f32.data_ptr(), off.data_ptr(),
-                                                              ent.data_ptr(), gout.data_ptr(), work.data_ptr(), gv.data_ptr(),
-                                                              B, V, f32.shape[0], torch.cuda.current_stream().cuda_stream),
-                       "vertex_normals_bwd")
+        _lib.launch("gif_vertex_normals_bwd_f32", verts.device, verts, f32, off, ent, gout.contiguous().float(), work, gv, B, V,
+                    f32.shape[0])
         return gv.to(ctx.in_dtype), None, None, None
 
 
@@ -102,8 +119,7 @@ def vertex_normals(vertices, faces):
     """[B,V,3] float32, faces [F,3] or [B,F,3] (same topology for every sample) -> unit normals [B,V,3].
     Differentiable with respect to `vertices` (gif_vertex_normals_bwd_f32)."""
     assert vertices.ndimension() == 3 and vertices.shape[2] == 3
-    if not vertices.is_cuda:
-        raise _lib.GifHipError("vertex_normals needs device tensors (no CPU fallback)")
+    _lib.require_device("vertex_normals", vertices=vertices)
     f32, off, ent = _topology(faces, vertices.shape[1], vertices.device)
     return _VertexNormalsFn.apply(vertices, f32, off, ent)
 
@@ -115,74 +131,52 @@ def batch_orth_proj(X, camera):
     return camera[:, :, 0:1] * X_trans
 
 
-def _rasterize_colors(vertices_ndc, faces, face_colors_of, h, w, with_depth=False):
-    """The forward both attribute rasterisers share: (fv, fc, tri, image [B,3,h,w], mask [B,1,h,w]); `face_colors_of(faces_b)`
-    gives the per-face-corner attributes [B,F,3,3].  with_depth=True appends the depth buffer [B,h,w] (gif_amd.antialias)."""
-    B = vertices_ndc.shape[0]
-    faces_b = faces[None].expand(B, -1, -1) if faces.ndimension() == 2 else faces
-    v = sr.to_image_space(vertices_ndc.float(), h, w)
-    fv = sr.face_vertices(v, faces_b)
-    fc = face_colors_of(faces_b)
-    depth, tri, img = sr.new_buffers(B, h, w, vertices_ndc.device)
-    sr.standard_rasterize_colors(fv, fc, depth, tri, img, h, w)
-    out = (fv, fc, tri, img.permute(0, 3, 1, 2).contiguous(), (tri >= 0)[:, None])
-    return out + (depth,) if with_depth else out
+class _RasterizeColorsFn(Function):
+    """The one owner of gif_rasterize_colors_f32 and gif_rasterize_colors_bwd_f32: (image [B,3,h,w], mask [B,1,h,w], tri [B,h,w],
+    depth [B,h,w]), the last three without a gradient.  per_vertex: `attributes` [B,Va,3] are gathered through `faces`; else they
+    are given per face corner, [F,3,3] (shared by the batch) or [B,F,3,3].  `what` names the caller in a refusal."""
 
-
-def _rasterize_colors_bwd(fv, fc, tri, gimg, faces, V, vdtype, h, w, need_v, need_c, what):
-    """d image -> (d vertices_ndc [B,V,3] in `vdtype` or None, d face colours [B,F,3,3] or None): gif_rasterize_colors_bwd_f32,
-    then for the vertices the face gather's transpose and the NDC -> pixel scaling."""
-    B, F = fv.shape[:2]
-    if faces.ndimension() == 3 and B > 1 and faces.stride(0) != 0 and not torch.equal(faces, faces[:1].expand_as(faces)):
-        raise _lib.GifHipError(f"{what} backward needs one face topology for the whole batch")
-    dev = fv.device
-    lib = _lib.load()
-    g = gimg.float().permute(0, 2, 3, 1).contiguous()  # [B,H,W,3]: the forward's image buffer layout
-    gfv = torch.empty_like(fv) if need_v else None
-    gfc = torch.empty_like(fc) if need_c else None
-    ws = torch.empty((max(lib.gif_rasterize_colors_bwd_workspace_bytes(B, F, h, w) // 4, 1),), device=dev,
-                     dtype=torch.float32)
-    gv = None
-    with torch.cuda.device(dev):
-        _lib.check(lib.gif_rasterize_colors_bwd_f32(fv.data_ptr(), fc.data_ptr(), tri.data_ptr(), g.data_ptr(),
-                                                    gfv.data_ptr() if need_v else None,
-                                                    gfc.data_ptr() if need_c else None, B, F, h, w, ws.data_ptr(),
-                                                    torch.cuda.current_stream().cuda_stream), "rasterize_colors_bwd")
-        if need_v:
-            _, off, ent = _topology(faces, V, dev)
-            gv = _face_gather_bwd(gfv, off, ent, V)
-            # to_image_space: x * w/2 + w/2, y * h/2 + h/2; z only orders the faces (no gradient)
-            gv *= torch.tensor([w / 2, h / 2, 0.0], device=dev, dtype=torch.float32)
-            gv = gv.to(vdtype)
-    return gv, gfc
-
-
-class _RasterizeAttributesFn(Function):
     @staticmethod
-    def forward(ctx, vertices_ndc, attributes, faces, h, w):
-        fv, fc, tri, img, mask = _rasterize_colors(
-            vertices_ndc, faces, lambda faces_b: sr.face_vertices(attributes.float().contiguous(), faces_b), h, w)
-        ctx.mark_non_differentiable(mask)
+    def forward(ctx, vertices_ndc, attributes, faces, h, w, per_vertex, what):
+        B = vertices_ndc.shape[0]
+        fv = _projected_face_vertices(vertices_ndc, faces, h, w)
+        fc = attributes.float()
+        if per_vertex:
+            fc = sr.face_vertices(fc.contiguous(), _batched_faces(faces, B))
+        else:
+            fc = (fc[None].expand(B, -1, -1, -1) if fc.ndimension() == 3 else fc).contiguous()
+        depth, tri, img = sr.new_buffers(B, h, w, vertices_ndc.device)
+        sr.standard_rasterize_colors(fv, fc, depth, tri, img, h, w)
+        mask = (tri >= 0)[:, None]
+        ctx.mark_non_differentiable(mask, tri, depth)
+        ctx.set_materialize_grads(False)  # no zero tensors (a fill launch each) for the three outputs that carry no gradient
         ctx.save_for_backward(fv, fc, tri)
-        ctx.faces, ctx.hw = faces, (h, w)
+        ctx.faces, ctx.hw, ctx.per_vertex, ctx.what = faces, (h, w), per_vertex, what
         ctx.dtypes = (vertices_ndc.dtype, attributes.dtype)
-        ctx.V = (vertices_ndc.shape[1], attributes.shape[1])
-        return img, mask
+        ctx.V, ctx.attr_shape = vertices_ndc.shape[1], attributes.shape
+        return img.permute(0, 3, 1, 2).contiguous(), mask, tri, depth
 
     @staticmethod
     @once_differentiable  # raw kernel launch: a double backward must fail loudly, not return a history-free gradient
-    def backward(ctx, gimg, _gmask):
+    def backward(ctx, gimg, _gmask, _gtri, _gdepth):
         fv, fc, tri = ctx.saved_tensors
         faces, (h, w) = ctx.faces, ctx.hw
-        need_v, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gv, gfc = _rasterize_colors_bwd(fv, fc, tri, gimg, faces, ctx.V[0], ctx.dtypes[0], h, w, need_v, need_a,
-                                        "rasterize_attributes")
+        need_v, need_a = ctx.needs_input_grad[:2]
+        B, F = fv.shape[:2]
+        _one_topology(faces, B, ctx.what + " backward")
+        g = gimg.float().permute(0, 2, 3, 1).contiguous()  # [B,H,W,3]: the forward's image buffer layout
+        gfv = torch.empty_like(fv) if need_v else None
+        gfc = torch.empty_like(fc) if need_a else None
+        ws = _lib.workspace(_lib.load().gif_rasterize_colors_bwd_workspace_bytes(B, F, h, w), fv.device)
+        _lib.launch("gif_rasterize_colors_bwd_f32", fv.device, fv, fc, tri, g, gfv, gfc, B, F, h, w, ws)
+        gv = _ndc_vertex_grad(gfv, faces, ctx.V, h, w, ctx.dtypes[0]) if need_v else None
         ga = None
-        if need_a:
-            with torch.cuda.device(fv.device):
-                _, off, ent = _topology(faces, ctx.V[1], fv.device)
-                ga = _face_gather_bwd(gfc, off, ent, ctx.V[1]).to(ctx.dtypes[1])
-        return gv, ga, None, None, None
+        if need_a and ctx.per_vertex:
+            Va = ctx.attr_shape[1]
+            ga = _face_gather_bwd(gfc, *_topology(faces, Va, fv.device)[1:], Va).to(ctx.dtypes[1])
+        elif need_a:
+            ga = (gfc.sum(0) if len(ctx.attr_shape) == 3 else gfc).to(ctx.dtypes[1])
+        return gv, ga, None, None, None, None, None
 
 
 def rasterize_attributes(vertices_ndc, faces, attributes, h, w):
@@ -191,7 +185,7 @@ def rasterize_attributes(vertices_ndc, faces, attributes, h, w):
     Differentiable with respect to vertices_ndc (x, y) and attributes inside each pixel's winning face
     (gif_rasterize_colors_bwd_f32); no silhouette, occlusion-boundary or depth gradient.  The mask has no gradient.
     gif_amd.antialias.rasterize_attributes_aa is the opt-in variant whose outline carries a gradient."""
-    return _RasterizeAttributesFn.apply(vertices_ndc, attributes, faces, h, w)
+    return _RasterizeColorsFn.apply(vertices_ndc, attributes, faces, h, w, True, "rasterize_attributes")[:2]
 
 
 def quantize_8bit(img01):

@@ -35,10 +35,7 @@ class _ShShadeFn(Function):
         alb, sh = albedo.contiguous().float(), sh_coeff.contiguous().float()
         m8 = mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else (mask != 0).contiguous().view(torch.uint8)
         out = torch.empty((B, 3, H, W), device=uv.device, dtype=torch.float32)
-        with torch.cuda.device(uv.device):  # launch on the operands' device and its current stream
-            _lib.check(_lib.load().gif_shade_sh_f32(uv.data_ptr(), nrm.data_ptr(), m8.data_ptr(), alb.data_ptr(), sh.data_ptr(),
-                                                    out.data_ptr(), B, alb.shape[0], H, W, alb.shape[2], nrm_mul, nrm_add,
-                                                    torch.cuda.current_stream().cuda_stream), "shade_sh")
+        _lib.launch("gif_shade_sh_f32", uv.device, uv, nrm, m8, alb, sh, out, B, alb.shape[0], H, W, alb.shape[2], nrm_mul, nrm_add)
         ctx.save_for_backward(uv, nrm, m8, alb, sh)
         ctx.scale = (float(nrm_mul), float(nrm_add))
         ctx.dtypes = (uv_img.dtype, normal_img.dtype, albedo.dtype, sh_coeff.dtype)
@@ -51,17 +48,10 @@ class _ShShadeFn(Function):
         B, _, H, W = uv.shape
         need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3], ctx.needs_input_grad[4])
         g = g_out.contiguous().float()
-        dev = g.device
-        lib = _lib.load()
         outs = [torch.empty_like(t) if n else None for t, n in zip((uv, nrm, alb, sh), need)]  # only what autograd asks for
-        ws = torch.empty((max(lib.gif_shade_sh_bwd_workspace_bytes(B, H, W) // 4, 1),), device=dev,
-                         dtype=torch.float32) if need[3] else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(lib.gif_shade_sh_bwd_f32(uv.data_ptr(), nrm.data_ptr(), m8.data_ptr(), alb.data_ptr(), sh.data_ptr(),
-                                                g.data_ptr(), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), B,
-                                                alb.shape[0], H, W, alb.shape[2], ctx.scale[0], ctx.scale[1], ptr(ws),
-                                                torch.cuda.current_stream().cuda_stream), "shade_sh_bwd")
+        ws = _lib.workspace(_lib.load().gif_shade_sh_bwd_workspace_bytes(B, H, W), g.device) if need[3] else None
+        _lib.launch("gif_shade_sh_bwd_f32", g.device, uv, nrm, m8, alb, sh, g, *outs, B, alb.shape[0], H, W, alb.shape[2],
+                    *ctx.scale, ws)
         g_uv, g_nrm, g_alb, g_sh = (None if t is None else t.to(dt) for t, dt in zip(outs, ctx.dtypes))
         return g_uv, g_nrm, None, g_alb, g_sh, None, None
 
@@ -73,11 +63,7 @@ def sh_shade(uv_img, normal_img, mask, albedo, sh_coeff, nrm_mul=1.0, nrm_add=0.
     n = nrm_mul * normal_img + nrm_add (not re-normalised); 0 outside the mask.  Differentiable with respect to uv_img, normal_img,
     albedo and sh_coeff; only the gradients autograd asks for are computed.  The gradient to `albedo` is accumulated with float
     atomics (last bits vary from run to run); everything else is deterministic."""
-    for name, t in (("uv_img", uv_img), ("normal_img", normal_img), ("mask", mask), ("albedo", albedo), ("sh_coeff", sh_coeff)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.GifHipError(f"sh_shade needs device tensors ({name} is not one; no CPU fallback)")
-        if t.device != uv_img.device:
-            raise _lib.GifHipError(f"{name} is on {t.device}, uv_img on {uv_img.device}")
+    _lib.require_device("sh_shade", uv_img=uv_img, normal_img=normal_img, mask=mask, albedo=albedo, sh_coeff=sh_coeff)
     if uv_img.ndimension() != 4 or uv_img.shape[1] != 3:
         raise ValueError(f"uv_img must be [B,3,H,W], got {list(uv_img.shape)}")
     B, _, H, W = uv_img.shape
@@ -92,45 +78,17 @@ def sh_shade(uv_img, normal_img, mask, albedo, sh_coeff, nrm_mul=1.0, nrm_add=0.
     return _ShShadeFn.apply(uv_img, normal_img, mask, albedo, sh_coeff, float(nrm_mul), float(nrm_add))
 
 
-class _RasterizeFaceAttributesFn(Function):
-    @staticmethod
-    def forward(ctx, vertices_ndc, face_attributes, faces, h, w):
-        B = vertices_ndc.shape[0]
-        shared = face_attributes.ndimension() == 3
-        fa = face_attributes.float()
-        fv, fc, tri, img, mask = render._rasterize_colors(
-            vertices_ndc, faces, lambda faces_b: (fa[None].expand(B, -1, -1, -1) if shared else fa).contiguous(), h, w)
-        ctx.mark_non_differentiable(mask)
-        ctx.save_for_backward(fv, fc, tri)
-        ctx.faces, ctx.hw, ctx.shared = faces, (h, w), shared
-        ctx.dtypes = (vertices_ndc.dtype, face_attributes.dtype)
-        ctx.V = vertices_ndc.shape[1]
-        return img, mask
-
-    @staticmethod
-    @once_differentiable  # raw kernel launch: a double backward must fail loudly, not return a history-free gradient
-    def backward(ctx, gimg, _gmask):
-        fv, fc, tri = ctx.saved_tensors
-        (h, w) = ctx.hw
-        gv, gfc = render._rasterize_colors_bwd(fv, fc, tri, gimg, ctx.faces, ctx.V, ctx.dtypes[0], h, w,
-                                               ctx.needs_input_grad[0], ctx.needs_input_grad[1], "rasterize_face_attributes")
-        if gfc is not None:
-            gfc = (gfc.sum(0) if ctx.shared else gfc).to(ctx.dtypes[1])
-        return gv, gfc, None, None, None
-
-
 def rasterize_face_attributes(vertices_ndc, faces, face_attributes, h, w):
     """render.rasterize_attributes for attributes given per FACE CORNER, [F,3,3] (shared by the batch) or [B,F,3,3]: a UV chart has
     its own topology (two faces that share a vertex across a seam give it different coordinates), so the attribute cannot be
-    per vertex.  Same launches, same conventions, same limits of the gradient (inside each pixel's winning face), which goes to
-    vertices_ndc and, if asked, to face_attributes.  -> (images [B,3,h,w], mask [B,1,h,w])."""
-    if not vertices_ndc.is_cuda or not face_attributes.is_cuda:
-        raise _lib.GifHipError("rasterize_face_attributes needs device tensors (no CPU fallback)")
+    per vertex.  Same launches (render._RasterizeColorsFn), same conventions, same limits of the gradient (inside each pixel's
+    winning face), which goes to vertices_ndc and, if asked, to face_attributes.  -> (images [B,3,h,w], mask [B,1,h,w])."""
+    _lib.require_device("rasterize_face_attributes", vertices_ndc=vertices_ndc, face_attributes=face_attributes)
     F = faces.shape[-2]
     want = ((F, 3, 3), (vertices_ndc.shape[0], F, 3, 3))
     if tuple(face_attributes.shape) not in want:
         raise ValueError(f"face_attributes must be {list(want[0])} or {list(want[1])}, got {list(face_attributes.shape)}")
-    return _RasterizeFaceAttributesFn.apply(vertices_ndc, face_attributes, faces, h, w)
+    return render._RasterizeColorsFn.apply(vertices_ndc, face_attributes, faces, h, w, False, "rasterize_face_attributes")[:2]
 
 
 def render_shaded_condition(vertices_ndc, faces, face_uvs, albedo, sh_coeff, h=256, w=256, straight_through=False):

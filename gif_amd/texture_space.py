@@ -19,20 +19,14 @@ from . import render
 class _TextureMapFn(Function):
     @staticmethod
     def forward(ctx, img, verts, normals, cam, tmap, tfaces, tbc, T):
-        lib = _lib.load()
-        if not img.is_cuda:
-            raise _lib.GifHipError("compute_texture_map needs device tensors (no CPU fallback)")
+        _lib.require_device("compute_texture_map", source_img=img)
         img = img.contiguous().float()
         verts, normals, cam = verts.contiguous().float(), normals.contiguous().float(), cam.contiguous().float().view(-1, 3)
         B, C, H, W = img.shape
         V = verts.shape[1]
         tex = torch.empty((B, C, T, T), device=img.device, dtype=torch.float32)
         mask = torch.empty((B, 1, T, T), device=img.device, dtype=torch.uint8)
-        with torch.cuda.device(img.device):  # launch on the operands' device and its current stream
-            _lib.check(lib.gif_texture_map_f32(img.data_ptr(), verts.data_ptr(), normals.data_ptr(), cam.data_ptr(),
-                                               tmap.data_ptr(), tfaces.data_ptr(), tbc.data_ptr(), tex.data_ptr(),
-                                               mask.data_ptr(), B, C, H, W, V, T, torch.cuda.current_stream().cuda_stream),
-                       "texture_map")
+        _lib.launch("gif_texture_map_f32", img.device, img, verts, normals, cam, tmap, tfaces, tbc, tex, mask, B, C, H, W, V, T)
         ctx.save_for_backward(verts, normals, cam, tmap, tfaces, tbc)
         ctx.dims = (B, C, H, W, V, T)
         mask = mask.view(torch.bool)  # the kernel writes 0 / 1 bytes; the reference returns a bool mask (stg2_generator.py:415)
@@ -44,13 +38,9 @@ class _TextureMapFn(Function):
     def backward(ctx, gtex, _gmask):
         verts, normals, cam, tmap, tfaces, tbc = ctx.saved_tensors
         B, C, H, W, V, T = ctx.dims
-        lib = _lib.load()
-        gtex = gtex.contiguous()
         gimg = torch.empty((B, C, H, W), device=gtex.device, dtype=torch.float32)
-        with torch.cuda.device(gtex.device):
-            _lib.check(lib.gif_texture_map_bwd_f32(gtex.data_ptr(), verts.data_ptr(), normals.data_ptr(), cam.data_ptr(),
-                                                   tmap.data_ptr(), tfaces.data_ptr(), tbc.data_ptr(), gimg.data_ptr(), B, C, H,
-                                                   W, V, T, torch.cuda.current_stream().cuda_stream), "texture_map_bwd")
+        _lib.launch("gif_texture_map_bwd_f32", gtex.device, gtex.contiguous(), verts, normals, cam, tmap, tfaces, tbc, gimg,
+                    B, C, H, W, V, T)
         return gimg, None, None, None, None, None, None, None
 
 
