@@ -79,7 +79,8 @@ class _AntialiasFn(Function):
         tri, depth = tri.contiguous(), depth.float().contiguous()
         out = torch.empty_like(img)
         walk = ("gif_antialias_walk_f32", max_hops) if max_hops else ("gif_antialias_f32",)
-        _lib.launch(walk[0], img.device, img, tri, depth, fv, adj, out, B, C, fv.shape[1], h, w, *walk[1:])
+        if C:  # (no channel: nothing to blend, and the entry points take C >= 1)
+            _lib.launch(walk[0], img.device, img, tri, depth, fv, adj, out, B, C, fv.shape[1], h, w, *walk[1:])
         ctx.save_for_backward(img, tri, depth, fv, adj)
         ctx.faces, ctx.V, ctx.max_hops = faces, vertices_ndc.shape[1], max_hops
         ctx.dtypes = (image.dtype, vertices_ndc.dtype)
@@ -95,6 +96,9 @@ class _AntialiasFn(Function):
         if not (need_i or need_v):
             return None, None, None, None, None, None
         gi = torch.empty_like(img) if need_i else None
+        if C == 0:  # no channel carries a gradient to a vertex
+            gv = torch.zeros((B, ctx.V, 3), device=img.device, dtype=ctx.dtypes[1]) if need_v else None
+            return (gi.to(ctx.dtypes[0]) if need_i else None), gv, None, None, None, None
         gfv = torch.empty_like(fv) if need_v else None
         # (the workspace serves the vertex gradient alone: one element without it)
         ws = _lib.workspace(_lib.load().gif_antialias_bwd_workspace_bytes(B, F, h, w) if need_v else 0, img.device)
@@ -105,15 +109,15 @@ class _AntialiasFn(Function):
 
 
 def antialias(image, tri, depth, vertices_ndc, faces, max_hops=0):
-    """image [B,C,h,w] (any C >= 1) with the rasteriser's tri [B,h,w] int32 and depth [B,h,w] for vertices_ndc [B,V,3] and faces
-    [F,3] or [B,F,3] (one topology) -> [B,C,h,w]: pixel pairs that straddle a silhouette edge blended by the edge's sub-pixel
-    position (definition: include/gif_hip.h).  Differentiable with respect to image and to x, y of
-    vertices_ndc; not twice.  max_hops (0 .. 64) > 0: a pair whose front face does not own the outline edge walks on across up to
-    that many non-silhouette edges to the face that does; 0 is §3o's definition and its kernels."""
+    """image [B,C,h,w] (any C; C = 0 gives the empty image back) with the rasteriser's tri [B,h,w] int32 and depth [B,h,w] for
+    vertices_ndc [B,V,3] and faces [F,3] or [B,F,3] (one topology) -> [B,C,h,w]: pixel pairs that straddle a silhouette edge
+    blended by the edge's sub-pixel position (definition: include/gif_hip.h).  Differentiable with respect to image
+    and to x, y of vertices_ndc; not twice.  max_hops (0 .. 64) > 0: a pair whose front face does not own the outline edge walks on
+    across up to that many non-silhouette edges to the face that does; 0 is §3o's definition and its kernels."""
     max_hops = _check_hops(max_hops, "antialias")
     _lib.require_device("antialias", image=image, tri=tri, depth=depth, vertices_ndc=vertices_ndc, faces=faces)
-    if image.ndimension() != 4 or image.shape[1] < 1 or tri.shape != (image.shape[0],) + image.shape[2:] or tri.shape != depth.shape:
-        raise _lib.GifHipError("antialias: image [B,C,h,w] with C >= 1, tri and depth [B,h,w]")
+    if image.ndimension() != 4 or tri.shape != (image.shape[0],) + image.shape[2:] or tri.shape != depth.shape:
+        raise _lib.GifHipError("antialias: image [B,C,h,w], tri and depth [B,h,w]")
     if tri.dtype != torch.int32:
         raise _lib.GifHipError(f"tri must be int32, got {tri.dtype}")
     if vertices_ndc.ndimension() != 3 or vertices_ndc.shape[0] != image.shape[0] or vertices_ndc.shape[2] != 3:

@@ -145,12 +145,22 @@ __global__ void __launch_bounds__(256) face_gather_bwd_kernel(const float* __res
     gvert[i * 3 + 2] = acc.z;
 }
 
+// `n` floats of exact zeros: what an entry point gives for a mesh without faces (faces and csr_ent are then empty arrays, whose
+// address may be null — no kernel is launched on them)
+int zero_fill(const char* who, float* out, size_t n, gif_stream_t stream) {
+    GIF_REQUIRE(out, "%s: null output", who);
+    hipError_t e = hipMemsetAsync(out, 0, n * sizeof(float), gif::as_stream(stream));
+    if (e != hipSuccess) { gif::set_error("%s memset: %s", who, hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int gif_vertex_normals_f32(const float* verts, const int32_t* faces, const int32_t* csr_off,
                                       const int32_t* csr_ent, float* normals, int B, int V, int F, gif_stream_t stream) {
-    GIF_REQUIRE(B >= 0 && V > 0 && F >= 0, "vertex_normals: bad dims");
-    if (B == 0) return 0;
+    GIF_REQUIRE(B >= 0 && V >= 0 && F >= 0, "vertex_normals: bad dims");
+    if ((long)B * V == 0) return 0;
+    if (F == 0) return zero_fill("vertex_normals", normals, (size_t)B * V * 3, stream);  // x / max(|x|, eps) of an empty sum
     GIF_REQUIRE(verts && faces && csr_off && csr_ent && normals, "vertex_normals: null pointer");
     vertex_normals_kernel<<<gif::cdiv((long)B * V, 256), 256, 0, gif::as_stream(stream)>>>(verts, faces, csr_off, csr_ent,
                                                                                             normals, B, V);
@@ -160,8 +170,9 @@ extern "C" int gif_vertex_normals_f32(const float* verts, const int32_t* faces, 
 extern "C" int gif_vertex_normals_bwd_f32(const float* verts, const int32_t* faces, const int32_t* csr_off,
                                           const int32_t* csr_ent, const float* grad_normals, float* work, float* grad_verts,
                                           int B, int V, int F, gif_stream_t stream) {
-    GIF_REQUIRE(B >= 0 && V > 0 && F >= 0, "vertex_normals_bwd: bad dims");
-    if (B == 0) return 0;
+    GIF_REQUIRE(B >= 0 && V >= 0 && F >= 0, "vertex_normals_bwd: bad dims");
+    if ((long)B * V == 0) return 0;
+    if (F == 0) return zero_fill("vertex_normals_bwd", grad_verts, (size_t)B * V * 3, stream);  // no vertex moves a normal
     GIF_REQUIRE(verts && faces && csr_off && csr_ent && grad_normals && work && grad_verts, "vertex_normals_bwd: null pointer");
     GIF_REQUIRE(work != grad_verts && work != grad_normals, "vertex_normals_bwd: work must not alias an operand");
     hipStream_t s = gif::as_stream(stream);
@@ -173,8 +184,9 @@ extern "C" int gif_vertex_normals_bwd_f32(const float* verts, const int32_t* fac
 
 extern "C" int gif_face_gather_bwd_f32(const float* grad_face, const int32_t* csr_off, const int32_t* csr_ent,
                                        float* grad_vertex, int B, int V, int F, gif_stream_t stream) {
-    GIF_REQUIRE(B >= 0 && V > 0 && F >= 0, "face_gather_bwd: bad dims");
-    if (B == 0) return 0;
+    GIF_REQUIRE(B >= 0 && V >= 0 && F >= 0, "face_gather_bwd: bad dims");
+    if ((long)B * V == 0) return 0;
+    if (F == 0) return zero_fill("face_gather_bwd", grad_vertex, (size_t)B * V * 3, stream);  // empty sums
     GIF_REQUIRE(grad_face && csr_off && csr_ent && grad_vertex, "face_gather_bwd: null pointer");
     face_gather_bwd_kernel<<<gif::cdiv((long)B * V, 256), 256, 0, gif::as_stream(stream)>>>(grad_face, csr_off, csr_ent,
                                                                                              grad_vertex, B, V, F);
@@ -310,9 +322,14 @@ __global__ void __launch_bounds__(256) texture_map_bwd_kernel(const TexParams p)
 extern "C" int gif_texture_map_f32(const float* img, const float* verts, const float* normals, const float* cam,
                                    const int32_t* texel_map, const int32_t* texel_faces, const float* texel_bc, float* tex,
                                    uint8_t* mask, int B, int C, int H, int W, int V, int T, gif_stream_t stream) {
-    GIF_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && V > 0 && T > 0, "texture_map: bad dims");
+    GIF_REQUIRE(B >= 0 && C >= 0 && H > 0 && W > 0 && V >= 0 && T > 0, "texture_map: bad dims (B=%d C=%d H=%d W=%d V=%d T=%d)", B, C,
+                H, W, V, T);
     if (B == 0) return 0;
-    GIF_REQUIRE(img && verts && normals && cam && texel_map && texel_faces && texel_bc && tex && mask, "texture_map: null pointer");
+    // C == 0: no image plane is read or written, the mask is still computed.  texel_faces / texel_bc are the arrays of an EMPTY
+    // valid-texel list when null (the caller guarantees that texel_map then holds -1 alone, so neither is read: include/gif_hip.h);
+    // so are verts / normals of V == 0 vertices.
+    GIF_REQUIRE((C == 0 || (img && tex)) && (V == 0 || (verts && normals)) && cam && texel_map && mask && !texel_faces == !texel_bc,
+                "texture_map: null pointer");
     TexParams p{};
     p.img = img; p.verts = verts; p.normals = normals; p.cam = cam; p.map = texel_map; p.faces = texel_faces; p.bc = texel_bc;
     p.tex = tex; p.mask = mask; p.B = B; p.C = C; p.H = H; p.W = W; p.V = V; p.T = T;
@@ -323,9 +340,11 @@ extern "C" int gif_texture_map_f32(const float* img, const float* verts, const f
 extern "C" int gif_texture_map_bwd_f32(const float* gtex, const float* verts, const float* normals, const float* cam,
                                        const int32_t* texel_map, const int32_t* texel_faces, const float* texel_bc,
                                        float* gimg, int B, int C, int H, int W, int V, int T, gif_stream_t stream) {
-    GIF_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && V > 0 && T > 0, "texture_map_bwd: bad dims");
-    if (B == 0) return 0;
-    GIF_REQUIRE(gtex && verts && normals && cam && texel_map && texel_faces && texel_bc && gimg, "texture_map_bwd: null pointer");
+    GIF_REQUIRE(B >= 0 && C >= 0 && H > 0 && W > 0 && V >= 0 && T > 0, "texture_map_bwd: bad dims (B=%d C=%d H=%d W=%d V=%d T=%d)", B,
+                C, H, W, V, T);
+    if ((long)B * C == 0) return 0;
+    GIF_REQUIRE(gtex && (V == 0 || (verts && normals)) && cam && texel_map && gimg && !texel_faces == !texel_bc,
+                "texture_map_bwd: null pointer");  // (null texel_faces / texel_bc: an empty valid-texel list, as in the forward)
     hipStream_t s = gif::as_stream(stream);
     hipError_t me = hipMemsetAsync(gimg, 0, (size_t)B * C * H * W * sizeof(float), s);
     if (me != hipSuccess) { gif::set_error("texture_map_bwd memset: %s", hipGetErrorString(me)); return (int)me; }

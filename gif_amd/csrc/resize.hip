@@ -94,9 +94,11 @@ extern "C" {
 
 // x [planes, Hi, Wi] -> y [planes, Ho, Wo]  (planes = B*C of an NCHW tensor); mode 0 = bilinear, 1 = bicubic
 int gif_resize_f32(const float* x, float* y, int64_t planes, int Hi, int Wi, int Ho, int Wo, int mode, gif_stream_t stream) {
-    GIF_REQUIRE(x && y && planes >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "resize: bad arguments");
+    GIF_REQUIRE(planes >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "resize: bad dims (planes=%ld Hi=%d Wi=%d Ho=%d Wo=%d)",
+                (long)planes, Hi, Wi, Ho, Wo);
     GIF_REQUIRE(mode == 0 || mode == 1, "resize: mode must be 0 (bilinear) or 1 (bicubic)");
-    if (planes == 0) return 0;
+    if (planes == 0) return 0;  // (before the pointers: an empty tensor's address may be null)
+    GIF_REQUIRE(x && y, "resize: null pointer");
     long total = planes * Ho * Wo;
     long blocks = (total + 255) / 256;
     if (blocks > 256 * 64) blocks = 256 * 64;
@@ -108,9 +110,11 @@ int gif_resize_f32(const float* x, float* y, int64_t planes, int Hi, int Wi, int
 // gx [planes, Hi, Wi] (zeroed inside) += adjoint of the resize applied to gy [planes, Ho, Wo]
 int gif_resize_bwd_f32(const float* gy, float* gx, int64_t planes, int Hi, int Wi, int Ho, int Wo, int mode,
                        gif_stream_t stream) {
-    GIF_REQUIRE(gy && gx && planes >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "resize_bwd: bad arguments");
+    GIF_REQUIRE(planes >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "resize_bwd: bad dims (planes=%ld Hi=%d Wi=%d Ho=%d Wo=%d)",
+                (long)planes, Hi, Wi, Ho, Wo);
     GIF_REQUIRE(mode == 0 || mode == 1, "resize_bwd: mode must be 0 (bilinear) or 1 (bicubic)");
     if (planes == 0) return 0;
+    GIF_REQUIRE(gy && gx, "resize_bwd: null pointer");
     hipStream_t s = gif::as_stream(stream);
     if (hipMemsetAsync(gx, 0, (size_t)planes * Hi * Wi * sizeof(float), s) != hipSuccess) return gif::check_launch("resize_bwd memset");
     long total = planes * Ho * Wo;

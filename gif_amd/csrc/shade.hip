@@ -271,6 +271,10 @@ extern "C" int gif_shade_sh_bwd_f32(const float* uv, const float* nrm, const uin
         hipError_t me = hipMemsetAsync(g_albedo, 0, (size_t)Ba * 3 * T * T * sizeof(float), s);
         if (me != hipSuccess) { gif::set_error("shade_sh_bwd memset: %s", hipGetErrorString(me)); return (int)me; }
     }
+    if (rc == 1 && g_sh && B > 0) {  // no pixel: 27 empty sums per sample (no kernel runs that would write them)
+        hipError_t me = hipMemsetAsync(g_sh, 0, (size_t)B * 27 * sizeof(float), s);
+        if (me != hipSuccess) { gif::set_error("shade_sh_bwd memset: %s", hipGetErrorString(me)); return (int)me; }
+    }
     if (!work) return 0;
     ShadeBwd a{};
     a.uv = uv; a.nrm = nrm; a.albedo = albedo; a.sh = sh; a.g_out = g_out; a.mask = mask;

@@ -19,27 +19,28 @@ from . import ops
 class _ResizeFn(Function):
     @staticmethod
     def forward(ctx, x, out_hw, mode):
-        ctx.in_hw, ctx.out_hw, ctx.mode = tuple(x.shape[2:]), tuple(out_hw), mode
-        return ops.resize(x, out_hw, mode)
+        ctx.in_hw, ctx.out_hw, ctx.mode, ctx.dtype = tuple(x.shape[2:]), tuple(out_hw), mode, x.dtype
+        return ops.resize(x.float(), out_hw, mode)
 
     @staticmethod
     def backward(ctx, gy):
-        return _ResizeBwdFn.apply(gy, ctx.in_hw, ctx.out_hw, ctx.mode), None, None
+        return _ResizeBwdFn.apply(gy, ctx.in_hw, ctx.out_hw, ctx.mode).to(ctx.dtype), None, None
 
 
 class _ResizeBwdFn(Function):  # linear map: its backward is the forward resize again
     @staticmethod
     def forward(ctx, gy, in_hw, out_hw, mode):
-        ctx.out_hw, ctx.mode = out_hw, mode
-        return ops.resize(gy, None, mode, backward_to=in_hw)
+        ctx.out_hw, ctx.mode, ctx.dtype = out_hw, mode, gy.dtype
+        return ops.resize(gy.float(), None, mode, backward_to=in_hw)
 
     @staticmethod
     def backward(ctx, ggx):
-        return _ResizeFn.apply(ggx, ctx.out_hw, ctx.mode), None, None, None
+        return _ResizeFn.apply(ggx, ctx.out_hw, ctx.mode).to(ctx.dtype), None, None, None
 
 
 def resize_image(x, out_hw, mode='bilinear'):
-    """F.interpolate(x, size=out_hw, mode=mode, align_corners=False) for any ratio, up or down (fp32 [B,C,H,W]; NCHW result);
+    """F.interpolate(x, size=out_hw, mode=mode, align_corners=False) for any ratio, up or down ([B,C,H,W], computed in fp32 like
+    every op of the library: another floating dtype is cast, and its gradient comes back in that dtype; fp32 NCHW result);
     differentiable to any order."""
     return _ResizeFn.apply(x, tuple(out_hw), mode)
 

@@ -252,7 +252,7 @@ def joint_basis(model, n_shape, n_exp):
     tmpl = np.asarray(model.v_template, np.float32)
     jr = np.asarray(model.J_regressor, np.float32).astype(np.float64)
     J0 = jr @ tmpl.astype(np.float64)
-    Jdirs = np.einsum("jv,vik->kji", jr, sd.astype(np.float64)).reshape(sd.shape[2], -1)
+    Jdirs = np.einsum("jv,vik->kji", jr, sd.astype(np.float64)).reshape(sd.shape[2], 3 * jr.shape[0])  # (no -1: K may be 0)
     return tmpl, sd, J0, Jdirs
 
 
@@ -377,7 +377,7 @@ class FlameLayer(nn.Module):
             if ids.size and (ids.min() < 0 or ids.max() >= V):
                 raise ValueError(f"vertex_ids outside 0..{V - 1}")
             tmpl, lbs_w = tmpl[ids], lbs_w[ids]
-            dirs = dirs.reshape(-1, V, 3)[:, ids].reshape(dirs.shape[0], 3 * len(ids))
+            dirs = dirs.reshape(dirs.shape[0], V, 3)[:, ids].reshape(dirs.shape[0], 3 * len(ids))
             V = len(ids)
         self.parents = tuple(int(p) for p in model.parents)
         self._parents_c = (ctypes.c_int32 * J)(*self.parents)

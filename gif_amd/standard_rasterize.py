@@ -68,7 +68,8 @@ def to_image_space(vertices, h, w):
     v = vertices.clone()
     v[..., 0] = v[..., 0] * w / 2 + w / 2
     v[..., 1] = v[..., 1] * h / 2 + h / 2
-    v[..., 2] = v[..., 2] - v[..., 2].min() + 1
+    if v.numel():  # (no vertex: nothing to shift, and min() of nothing raises)
+        v[..., 2] = v[..., 2] - v[..., 2].min() + 1
     return v
 
 

@@ -189,7 +189,10 @@ int gif_vertex_normals_bwd_f32(const float* verts, const int32_t* faces, const i
                                const float* grad_normals, float* work, float* grad_verts, int B, int V, int F,
                                gif_stream_t stream);
 /* Backward of the face gather vertices [B,V,3] -> face_vertices [B,F,3,3] (standard_rasterize.face_vertices):
- * grad_vertex[b,v] = sum over v's CSR entries (face*4 + corner) of grad_face[b,face,corner], in CSR order (no atomics). */
+ * grad_vertex[b,v] = sum over v's CSR entries (face*4 + corner) of grad_face[b,face,corner], in CSR order (no atomics).
+ * All three: B, V, F >= 0.  B * V == 0: no-op, before any pointer is looked at.  F == 0 (faces and csr_ent are then empty arrays
+ * and may be null): the output is set to exact zeros — the normal of an empty sum is 0 / max(0, eps), and no vertex receives a
+ * gradient. */
 int gif_face_gather_bwd_f32(const float* grad_face, const int32_t* csr_off, const int32_t* csr_ent, float* grad_vertex,
                             int B, int V, int F, gif_stream_t stream);
 
@@ -315,7 +318,11 @@ int gif_flame_landmarks_bwd_f32(const float* g_lmk, const int32_t* row, const in
  * (grid_sample, zero padding, align_corners=False), and the normal-z visibility mask.  img [B,C,H,W] NCHW; verts/normals
  * [B,V,3]; cam [B,3] = (scale, tx, ty); texel_map [T*T] = index into the valid-texel lists or -1 (those texels sample the
  * image centre, like the reference's zero grid); texel_faces [N,3] int32; texel_bc [N,3]; tex [B,C,T,T]; mask [B,1,T,T] u8.
- * The backward accumulates d tex / d img into gimg [B,C,H,W] (zeroed inside). */
+ * The backward accumulates d tex / d img into gimg [B,C,H,W] (zeroed inside).
+ * B, C, V >= 0; H, W, T > 0 (else GIF_EINVAL, "bad dims").  B == 0: no-op.  C == 0: the mask alone is computed (img, tex, gimg
+ * unused).  texel_faces and texel_bc null together: an empty valid-texel list — the CALLER guarantees that texel_map then holds
+ * -1 alone (an entry >= 0 would index the null arrays inside the kernel; like every index range, that is not checked).  V == 0:
+ * verts and normals unused. */
 int gif_texture_map_f32(const float* img, const float* verts, const float* normals, const float* cam,
                         const int32_t* texel_map, const int32_t* texel_faces, const float* texel_bc, float* tex,
                         uint8_t* mask, int B, int C, int H, int W, int V, int T, gif_stream_t stream);
@@ -345,10 +352,12 @@ int gif_texture_map_bwd_f32(const float* gtex, const float* verts, const float* 
  * g_sh is 27 sums over H*W per sample — one partial row per workgroup in `workspace` (gif_shade_sh_bwd_workspace_bytes(B, H, W)
  * bytes, 4-byte aligned, no initialisation needed), then a fixed-order sum; no float atomics, run-to-run identical bits.
  * g_albedo is NOT: it is zeroed inside and accumulated with fp32 atomicAdd (four taps x three channels per pixel; over the whole
- * batch when Ba == 1), so its last bits depend on arrival order — with gif_texture_map_bwd_f32 one of the two non-deterministic
- * backwards of the library, and like it never on the training step's or inference's path (labels are data there).
+ * batch when Ba == 1), so its last bits depend on arrival order — with gif_texture_map_bwd_f32 and gif_resize_bwd_f32 one of
+ * the three non-deterministic backwards of the library, and like them never on the training step's or inference's path (labels
+ * are data there).
  * B, H, W, T < 0, Ba outside {1, B}, B*3*H*W >= 2^31, a null required pointer, or (backward) T == 0 with g_albedo: GIF_EINVAL.
- * B*H*W == 0: no-op.  T == 0 (forward): every tap is outside, out = 0. */
+ * B*H*W == 0: the forward is a no-op; the backward writes the zeros of the empty sums to g_sh and g_albedo.
+ * T == 0 (forward): every tap is outside, out = 0. */
 int gif_shade_sh_f32(const float* uv, const float* nrm, const uint8_t* mask, const float* albedo, const float* sh, float* out,
                      int B, int Ba, int H, int W, int T, float nrm_mul, float nrm_add, gif_stream_t stream);
 int64_t gif_shade_sh_bwd_workspace_bytes(int B, int H, int W);
@@ -620,6 +629,7 @@ int gif_texture_pair_loss_bwd_f32(const float* a, const float* b, const uint8_t*
  * align_corners=False, no antialias) of the input / visualisation pipeline (generate_random_samples.py:190-191).
  * x [planes,Hi,Wi] -> y [planes,Ho,Wo] with planes = B*C of an NCHW fp32 tensor; mode 0 bilinear, 1 bicubic (A=-0.75,
  * border-clamped taps).  The backward scatters the same weights with fp32 atomics into gx (zeroed inside).
+ * planes >= 0; Hi, Wi, Ho, Wo > 0 (else GIF_EINVAL, "bad dims").  planes == 0: no-op, before the pointers are looked at.
  * ---------------------------------------------------------------------------------------------- */
 int gif_resize_f32(const float* x, float* y, int64_t planes, int Hi, int Wi, int Ho, int Wo, int mode,
                    gif_stream_t stream);

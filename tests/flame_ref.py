@@ -51,8 +51,8 @@ def flame_vertices(c, shape_params, expression_params, pose_params, neck_pose, e
     if return_joints:
         return joints
     R = rodrigues(full_pose(pose_params, neck_pose, eye_pose, J).reshape(B * J, 3)).view(B, J, 3, 3)
-    pose_feature = (R[:, 1:] - torch.eye(3, dtype=dt, device=dev)).reshape(B, -1)
-    v_posed = v_shaped + (pose_feature @ c["posedirs"]).view(B, -1, 3)
+    pose_feature = (R[:, 1:] - torch.eye(3, dtype=dt, device=dev)).reshape(B, 9 * (J - 1))  # (no -1: B may be 0)
+    v_posed = v_shaped + (pose_feature @ c["posedirs"]).view(B, v_shaped.shape[1], 3)
     bottom = torch.tensor([0, 0, 0, 1], dtype=dt, device=dev).expand(B, 1, 4)
     G = []
     for j, p in enumerate(c["parents"]):

@@ -4,7 +4,8 @@ of the algorithm in tests/flame_ref.py, at the sizes where they can go wrong:
   B in {1, 3, 33}           33 crosses the 32-sample chunk and leaves a chunk with one busy wave
   (n_shape, n_exp)          (7, 5): KP = 48 / 30; (100, 50): KP = 186 / 168, three 64-column passes; (300, 100): KP = 436, seven
   J = 5 (FLAME's parents) and J = 3 as the chain [-1, 0, 1]; neck and eye poses non-zero; one sample with an all-zero pose
-  (Rodrigues at its 1e-8 guard).
+  (Rodrigues at its 1e-8 guard).  The ends of the chain lengths the kernels take: J = 1 (no pose feature, KP == K, an empty
+  R[:, 1:]), J = 2 (the neck is the last joint) and J = 8 (kMaxJ; joints past the fifth do not rotate).
 
 Bound, forward and backward alike:  err <= M * err32 + 2^-23,  err32 = the same metric for the float32 restatement on the CPU
 with the same inputs (forward: max|got - ref| / max|ref|; backward: Frobenius, per parameter group).  M = 4.  It started at 8
@@ -20,6 +21,9 @@ MEASURED err / err32 on an MI355X (`pytest -s` prints them; forward: no-grad pat
   v257_b33_chain   0.89 / 0.88    0.77 (shape)
   v5023_b1         0.53 / 0.52    0.23 (neck)
   v5023_b33        0.73 / 0.73    0.65 (shape)
+  v33_b3_j1        1.00 / 1.00    1.39 (expression)
+  v33_b33_j2       0.92 / 0.93    1.29 (shape)
+  v257_b3_j8       0.81 / 1.22    0.47 (shape)
 err32 itself: 1.5e-7 .. 4.3e-7 forward; 8.6e-8 .. 1.1e-6 for shape / expression and 4.1e-7 .. 1.7e-5 for the poses backward (the
 largest at V = 1, where one vertex carries the whole cancellation).
 """
@@ -45,6 +49,10 @@ CASES = {
     "v257_b33_chain": (257, 33, (100, 50), CHAIN),
     "v5023_b1": (5023, 1, (7, 5), FLAME),
     "v5023_b33": (5023, 33, (100, 50), FLAME),
+    # the ends of the chain lengths the kernels take (J in 1..8; joints past the fifth do not rotate)
+    "v33_b3_j1": (33, 3, (7, 5), (-1,)),              # no pose feature (KP == K), an empty R[:, 1:]
+    "v33_b33_j2": (33, 33, (7, 5), (-1, 0)),          # the neck is the last joint
+    "v257_b3_j8": (257, 3, (7, 5), (-1, 0, 1, 1, 1, 0, 5, 2)),  # kMaxJ: three joints that do not rotate, 96 floats of A per sample
 }
 
 

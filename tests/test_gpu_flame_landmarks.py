@@ -6,7 +6,7 @@ The landmark step on given fp32 vertices and transforms (STEP):
   than a workgroup has lanes); every landmark on one face (V = 3: all contributions collide on three vertices); J = 5 and the
   chain (-1, 0, 1), yaw_joint = 1.  Two sizes beyond that list, for the backward's own thresholds: V = 2049 (three vertex ranges
   of 1024 per sample, the last one a single vertex) and Ld + Ls = 400 (1200 contributions: two staged tiles of 1024, five passes
-  of 256 lanes).
+  of 256 lanes).  Two chain lengths beyond J = 5 and 3: J = 1 (the yaw joint is the root, yaw_joint = 0) and J = 8 (kMaxJ).
   row      equal to the reference's;
   forward  per component |got - ref| <= 4 * 2^-24 * sum_i |bary_i v_i|           (three products, two adds, each rounded once);
   backward per element   |got - ref| <= (n + 1) * 2^-24 * sum |terms|, n = the number of contributions to the vertex (one product
@@ -25,8 +25,10 @@ backward: worst parameter group, FlameLayer then FlameLandmarkLayer):
   v33_b3_chain     0.75 / 0.75, 0.75 / 0.75     0.92 (neck), 1.02 (neck)             landmarks bit-equal, gradients not
   v257_b3_r1       0.85 / 0.85, 0.85 / 0.85     0.46 (eye), 0.43 (expression)        landmarks bit-equal, gradients not
   v257_b33_flame   0.68 / 0.70, 0.68 / 0.70     0.83 (expression), 0.79 (expression) landmarks bit-equal, gradients not
+  v257_b3_j8       0.74 / 0.74, 0.74 / 0.74     0.46 (shape), 0.54 (shape)           landmarks bit-equal, gradients not
 err32 itself: 8.5e-8 .. 2.8e-7 forward; 1.9e-7 .. 5.7e-7 for shape / expression and 8.3e-7 .. 3.1e-6 for the poses backward.
-The landmark step: forward worst |err| / bound 0.56, backward 0.58 (0.01 with 136 contributions on one vertex).
+The landmark step: forward worst |err| / bound 0.56, backward 0.58 (0.01 with 136 contributions on one vertex); the J = 1 and J = 8
+rows: forward 0.45 and 0.45, backward 0.40 and 0.46.
 """
 import math
 import os
@@ -43,6 +45,7 @@ U = 2.0 ** -24
 M_RULE, FLOOR = 4, 2.0 ** -23
 GROUPS = ("shape_params", "expression_params", "pose_params", "neck_pose", "eye_pose")
 FLAME, CHAIN = (-1, 0, 1, 1, 1), (-1, 0, 1)
+ROOT_ONLY, EIGHT = (-1,), (-1, 0, 1, 1, 1, 0, 5, 2)  # the ends of the chain lengths the kernels take (J in 1..8)
 YAWS = (0.0, -0.2, 12.3, 38.7, 45.0, -1.0, -12.3, -38.7, -45.0)
 ROWS39 = (0, 0, 12, 39, 39, 40, 51, 78, 78)
 
@@ -57,12 +60,15 @@ STEP = {
     "v257_b3_r79_ld17_ls283": (257, 3, 79, 17, 283, FLAME),      # Ld + Ls = 300
     "v3_b33_r79_ld17_ls119_one_face": (3, 33, 79, 17, 119, FLAME),  # every landmark on the same face
     "v2049_b3_r3_ld1_ls399": (2049, 3, 3, 1, 399, FLAME),         # three vertex ranges, two contribution tiles
+    "v33_b3_r3_ld1_ls1_j1": (33, 3, 3, 1, 1, ROOT_ONLY),          # J = 1: the yaw joint is the root (yaw_joint = 0)
+    "v257_b3_r79_ld17_ls119_j8": (257, 3, 79, 17, 119, EIGHT),    # J = 8: 96 floats of A per sample
 }
 # name: (V, B, (n_shape, n_exp), parents, (R, Ld, Ls, Lf))
 LAYER = {
     "v33_b3_chain": (33, 3, (7, 5), CHAIN, (3, 1, 1, 2)),
     "v257_b3_r1": (257, 3, (7, 5), FLAME, (1, 1, 119, 0)),
     "v257_b33_flame": (257, 33, (7, 5), FLAME, (79, 17, 51, 68)),
+    "v257_b3_j8": (257, 3, (7, 5), EIGHT, (79, 17, 51, 68)),
 }
 
 
@@ -113,18 +119,21 @@ def step_case(name):
     emb.check_vertices(V)
     t = lref.tables(emb, torch.float64)
     J, M = len(parents), (R - 1) // 2
+    yj = min(1, J - 1)  # the yaw joint: the neck, or the root of a one-joint chain (which then carries the whole prescribed yaw)
     g = torch.Generator().manual_seed(seed)
     verts = torch.randn(B, V, 3, generator=g)  # fp32: the kernel's input
     up = torch.randn(B, Ld + Ls, 3, generator=g)
     glob, neck, yaws = pose_rows(B, POSE_SEED.get(name, 0), offset=V + B)
     # A [B,J,12] in fp32: world rotations of the chain (global, neck, then seeded rotations) beside arbitrary translations
     rot = torch.randn(B, J, 3, generator=g, dtype=torch.float64) * 0.3
-    rot[:, 0], rot[:, 1] = glob, neck
+    rot[:, 0] = glob + neck if J == 1 else glob  # (both rotate about y: the sum is their product)
+    if J > 1:
+        rot[:, 1] = neck
     Rl = flame_ref.rodrigues(rot.reshape(B * J, 3)).view(B, J, 3, 3)
     GR = torch.stack([lref.world_rotation(Rl, parents, j) for j in range(J)], 1)
     A = torch.cat([GR, torch.randn(B, J, 3, 1, generator=g, dtype=torch.float64)], 3).reshape(B, J, 12).float()
     # float64 reference on the fp32 inputs
-    Rw = A.double().view(B, J, 3, 4)[:, 1, :, :3]
+    Rw = A.double().view(B, J, 3, 4)[:, yj, :, :3]
     yaw = lref.yaw_degrees(Rw)
     assert_rows_are_decided(yaw, M)
     l2d, _, row = lref.landmarks_of(t, verts.double(), Rw)
@@ -141,8 +150,8 @@ def step_case(name):
     g_ref = zeros().index_put_(idx, terms, accumulate=True)
     g_abs = zeros().index_put_(idx, terms.abs(), accumulate=True)
     count = zeros().index_put_(idx, torch.ones_like(terms), accumulate=True)
-    out = {"tables": t, "verts": verts, "A": A, "up": up, "dims": (V, B, R, Ld, Ls, J), "row": row, "lmk": l2d, "mag": mag,
-           "g_ref": g_ref, "g_abs": g_abs, "count": count}
+    out = {"tables": t, "verts": verts, "A": A, "up": up, "dims": (V, B, R, Ld, Ls, J), "yaw_joint": yj, "row": row, "lmk": l2d,
+           "mag": mag, "g_ref": g_ref, "g_abs": g_abs, "count": count}
     _cache[name] = out
     return out
 
@@ -153,7 +162,7 @@ def run_step(c, need_grad=True):
     t = c["tables"]
     dev = lambda a, dt: a.to(device="cuda", dtype=dt).contiguous() if a.numel() else None
     verts = c["verts"].cuda().requires_grad_(need_grad)
-    lmk, row = fl._FlameLandmarksFn.apply(verts, c["A"].cuda(), 1, R, Ld, Ls, dev(t["dynamic_vid"], torch.int32),
+    lmk, row = fl._FlameLandmarksFn.apply(verts, c["A"].cuda(), c["yaw_joint"], R, Ld, Ls, dev(t["dynamic_vid"], torch.int32),
                                           dev(t["dynamic_bary"], torch.float32), dev(t["static_vid"], torch.int32),
                                           dev(t["static_bary"], torch.float32))
     return verts, lmk, row
