@@ -97,8 +97,41 @@ struct ProfScope {
 // ---- fixed-order reduction of per-tile partial sums (elementwise.hip): out[y][c] = sum_k partial[y][k][c], y < Y, k < nblk.
 // Long single-group reductions (Y == 1, nblk > 512) go through `tmp` (>= 64 * C floats) in two launches.
 int reduce_partials(const float* partial, float* out, int Y, int nblk, int C, float* tmp, hipStream_t s);
-// partial rows an epilogue reduction may need for `rows` output rows (conv tiles of >= 64 rows, FIR blocks <= 4096) + tmp
-inline int64_t epilogue_ws_rows(int64_t rows) { return 2 * (rows / 64 + 16) + 4096 + 64; }
+// The red_ws workspace of an epilogue reduction over `rows` output rows.  epilogue_ws_rows and FusedSums describe the SAME buffer: `cap`
+// partial rows of column sums, `cap` of dot products (conv tiles of >= 64 rows), then tmp (FIR blocks <= 4096 rows + the 64 of
+// reduce_partials) — the first is what callers allocate (in rows of Co floats), the second how a convolution launch carves it up.
+inline int64_t epilogue_ws_cap(int64_t rows) { return rows / 64 + 16; }
+inline int64_t epilogue_ws_rows(int64_t rows) { return 2 * epilogue_ws_cap(rows) + 4096 + 64; }
+// Gradient-producer fusions of one convolution (direct or Winograd): carve the partial-sum buffers out of red_ws before the launches,
+// reduce them in a fixed order after.  The caller checks its own preconditions (what its tiles must divide) between the two.
+struct FusedSums {
+    float *colsum = nullptr, *dot = nullptr;          // the op's outputs (gif_conv_epilogue)
+    float *part_cs = nullptr, *part_dot = nullptr;    // what the kernels get: [cap][Co] each, NULL for a sum that is not asked for
+    float* tmp = nullptr;
+    long cap = 0;  // partial rows available per buffer
+
+    bool active() const { return colsum || dot; }
+    // rows = B * Ho * Wo of the op's output
+    int carve(const gif_conv_epilogue* e, long rows, int Co, const char* who) {
+        if (!e || (!e->colsum && !e->dot)) return 0;
+        GIF_REQUIRE(e->red_ws, "%s: colsum / dot need the red_ws workspace (gif_conv_epilogue_ws_floats)", who);
+        colsum = e->colsum;
+        dot = e->dot;
+        cap = (long)epilogue_ws_cap(rows);
+        part_cs = colsum ? e->red_ws : nullptr;
+        part_dot = dot ? e->red_ws + cap * Co : nullptr;
+        tmp = e->red_ws + 2 * cap * Co;
+        return 0;
+    }
+    // column sums over the `rows` partial rows the launches wrote, then the dot products of the B samples (rows_per_sample rows each)
+    int reduce(int rows, int Co, int B, int rows_per_sample, hipStream_t s) const {
+        if (colsum)
+            if (int rc = reduce_partials(part_cs, colsum, 1, rows, Co, tmp, s)) return rc;
+        if (dot)
+            if (int rc = reduce_partials(part_dot, dot, B, rows_per_sample, Co, tmp, s)) return rc;
+        return 0;
+    }
+};
 
 // ---- Winograd transforms (conv_winograd.hip), shared with the Winograd wgrad in conv_wgrad.hip ----
 // (padded dims of a transformed operand [16][ntiles_pad][CP]: wino_route.h padded_tiles / padded_channels)

@@ -29,14 +29,13 @@
 #include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_common.h"
 #include "conv_route.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: plain vector loads/stores, never memcpy
-
+using gif::f32x16, gif::f32x4, gif::xcd_remap;
+using gif::buf_rsrc_t, gif::make_buf_rsrc, gif::buf_load_lds16;  // (common.h; here always over the whole address range)
 
 // Activation / packed-weight pointers are typeless: fp32 (the reference dtype) or f16 (BASELINE config 5), chosen by the
 // kernel's element-type template parameter.  Per-sample scales and the bias are always fp32.
@@ -85,15 +84,6 @@ struct GatherParams {
     int dense;                 // bf16x3 kernels, 8 <= Ci < 32, 3x3: 16-byte chunks per tap (Ci / 4) of the tap-dense K order, else 0
     int t2_tx, t2_ty;          // halo kernel: 16 x 16-pixel patches per row / column of the output sub-grid
 };
-
-// XCD-aware, bijective block remap (cdna guide T1): consecutive logical tiles share an XCD's L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int nx = 8;
-    int xcd = bid % nx, idx = bid / nx;
-    int q = nwg / nx, r = nwg % nx;
-    int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
 
 // Epilogue shared by both kernels.  The accumulator tile is transposed through LDS (the staging buffers are free by
 // then) so that global I/O is row-wise float4: residual / out_scale / bias loads and the output store are 16 B per lane
@@ -279,7 +269,7 @@ __device__ __forceinline__ void conv_epilogue(const GatherParams& p, f32x16 (&ac
             }
             const int prow_i = p.part_row0 + (m0 - p.m_begin) / BM;
             const size_t prow = (size_t)prow_i * p.Co + n;
-            if (prow_i < p.part_cap) {  // never past the workspace: FusedSums::finish reports the overflow (tiles have >= 64 rows, so it cannot happen today)
+            if (prow_i < p.part_cap) {  // never past the workspace: sums_finish reports the overflow (tiles have >= 64 rows, so it cannot happen today)
                 if (p.part_cs) *reinterpret_cast<float4*>(p.part_cs + prow) = a;
                 if (p.part_dot) *reinterpret_cast<float4*>(p.part_dot + prow) = b;
             }
@@ -475,21 +465,8 @@ __global__ void __launch_bounds__(256) conv_gather_mfma(const GatherParams p) {
 //        16-byte chunks are XOR-swizzled with (row >> 2) & 3, so a B operand is one ds_read_b128 and costs no VALU.
 //        Six v_mfma_f32_32x32x16_bf16 per tile pair and 16 k-values.  On this chip VALU work does NOT hide under the MFMAs
 //        of the same SIMD (measured: time ~ MFMA + VALU), so the split work per MFMA is what bounds the kernel.
-// raw buffer descriptor (stride 0, num_records 2^32 - 1) + LDS-DMA through it: `buffer_load_dwordx4 v, s[rsrc], s_off offen lds`.
-// (The builtins exist in the device pass only; the host pass of this translation unit sees empty stand-ins.)
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_buf_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xFFFFFFFFu, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, __attribute__((address_space(3))) void* lds, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, lds, 16, (int)voff, soff, 0, 0);
-}
-#else
-struct buf_rsrc_t {};
-__device__ __forceinline__ buf_rsrc_t make_buf_rsrc(const void*) { return {}; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, __attribute__((address_space(3))) void*, unsigned, int) {}
-#endif
+// The operands go through raw buffer descriptors (common.h make_buf_rsrc / buf_load_lds16) over the whole address range (num_records
+// 2^32 - 1): `buffer_load_dwordx4 v, s[rsrc], s_off offen lds`.
 
 // NST: stages of the LDS operand ring.  2 everywhere except the 8-wave f16x2 kernel (one workgroup per CU: 3 x 48 KB fit), whose stage
 // is half as long as the bf16x3 one it replaced: with two stages the DMA of stage s + 1 is issued when stage s starts and a first-touch
@@ -672,8 +649,8 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
     // X3: raw buffer descriptors (stride 0, num_records = 2^32 - 1: validity is the lane's own out-of-range offset)
-    const buf_rsrc_t rs_a = make_buf_rsrc(px + (BUF ? min_off : 0));
-    const buf_rsrc_t rs_b = make_buf_rsrc(p.wp);
+    const buf_rsrc_t rs_a = make_buf_rsrc(px + (BUF ? min_off : 0), 0xFFFFFFFFu);
+    const buf_rsrc_t rs_b = make_buf_rsrc(p.wp, 0xFFFFFFFFu);
     // f16 weight tile: this lane's byte offset inside a tap's [RP][CP] slice (rows it * RPP further down go through the SGPR offset)
     const unsigned b_voff = b_lane_ok ? (unsigned)((n0 + t_row) * p.CP + src_c4) * (unsigned)sizeof(T) : 0xFFFFFFFFu;
 
@@ -1207,7 +1184,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_rows_thin_h2(const GatherParam
         for (int d = 0; d < 3; ++d) mk |= ((okx && (unsigned)(oy + d - 1) < (unsigned)p.Hi) ? 1u : 0u) << d;
         a_mask[it] = mk;
     }
-    const buf_rsrc_t rs_a = make_buf_rsrc(px - (size_t)p.Wi * p.Ci);
+    const buf_rsrc_t rs_a = make_buf_rsrc(px - (size_t)p.Wi * p.Ci, 0xFFFFFFFFu);
 
     const int kch = p.CP / 32, nst = 3 * kch;
     auto issue_a = [&](int buf, int st) __attribute__((always_inline)) {
@@ -1555,7 +1532,7 @@ static_assert(kRowsThinA == route::ROWS_THIN_A, "conv_route.h sizes the LDS of c
 const route::ConvKnobs& conv_knobs() {
     static const route::ConvKnobs once = [] {
         route::ConvKnobs k;
-        const auto num = [](const char* name, int unset) { const char* e = gif::knob(name); return e ? atoi(e) : unset; };
+        const auto num = gif::knob_int;
         k.h2_ring3 = num("GIF_H2_RING", 3) != 2;
         k.h2_rows_thin = num("GIF_H2_ROWS_THIN", 1) != 0;
         k.x3_waves = num("GIF_X3_WAVES", k.x3_waves);
@@ -1600,8 +1577,7 @@ GatherParams launch_params(const GatherParams& phase, const route::ConvLaunch& l
 
 template <typename K, typename P>
 void launch_kernel(K kern, gif::LdsAttr& attr, const route::ConvLaunch& l, const P& p, hipStream_t s) {
-    attr.ensure(reinterpret_cast<const void*>(kern), l.lds_bytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)l.grid), dim3(l.threads), l.lds_bytes, s, p);
+    gif::launch_lds(kern, attr, dim3((unsigned)l.grid), dim3(l.threads), l.lds_bytes, s, p);
 }
 
 // Each *_try launches its instantiation iff `l` names exactly it.
@@ -1745,22 +1721,6 @@ int check_geom(const gif_conv_geom* g, const char* who) {
     return 0;
 }
 
-void fill_epilogue(GatherParams& p, const gif_conv_epilogue* e) {
-    p.in_scale = e ? e->in_scale : nullptr;
-    p.out_scale = e ? e->out_scale : nullptr;
-    p.bias = e ? e->bias : nullptr;
-    p.residual = e ? e->residual : nullptr;
-    p.act = e ? e->act : 0;
-    p.slope = e ? e->slope : 0.f;
-    p.gain = e ? e->gain : 1.f;
-    p.mask_src = e ? e->mask_src : nullptr;
-    p.mask_slope = e ? e->mask_slope : 1.f;
-    p.mask_gain = e ? e->mask_gain : 1.f;
-    p.dot_src = e ? e->dot_src : nullptr;
-    p.sat_flag = nullptr;
-    p.out_f32 = e ? e->out_f32 : 0;
-}
-
 // tap-dense K order of the bf16x3 kernels (GatherParams::dense): 3x3 kernels over the full tap grid, contraction channels 8..28
 int check_tapdense(const gif_conv_geom* g, const gif_conv_epilogue* e, int cin, bool transposed, const char* who) {
     GIF_REQUIRE(gif_conv2d_x3_tapdense_steps(cin, g->KH, g->KW) > 0, "%s: tap-dense mode needs a 3x3 kernel and 8 <= Cin < 32 (got %dx%d, %d)",
@@ -1770,48 +1730,27 @@ int check_tapdense(const gif_conv_geom* g, const gif_conv_epilogue* e, int cin, 
     return 0;
 }
 
-// Gradient-producer fusions of one op: validate, carve the partial-sum buffers out of red_ws (before the launches) and reduce
-// them in a fixed order (after).  out_rows = B * Ho * Wo of the op's output.
-struct FusedSums {
-    float* colsum = nullptr;
-    float* dot = nullptr;
-    float* part_cs = nullptr;
-    float* part_dot = nullptr;
-    float* tmp = nullptr;
-    long cap = 0;  // partial rows available per buffer
-
-    bool active() const { return colsum || dot; }
-
-    int begin(GatherParams& p, const gif_conv_epilogue* e, long out_rows, int Co, long hw, bool single_phase, const char* who) {
-        if (!e || (!e->colsum && !e->dot)) return 0;
-        GIF_REQUIRE(e->red_ws, "%s: colsum / dot need the red_ws workspace (gif_conv_epilogue_ws_floats)", who);
-        GIF_REQUIRE(!e->dot || (e->dot_src && single_phase && hw % 256 == 0),
-                    "%s: the dot fusion needs dot_src, a single-phase op and a multiple of 256 output pixels per sample (got %ld)", who, hw);
-        colsum = e->colsum;
-        dot = e->dot;
-        cap = out_rows / 64 + 16;
-        part_cs = e->red_ws;
-        part_dot = e->red_ws + cap * Co;
-        tmp = e->red_ws + 2 * cap * Co;
-        p.part_cs = colsum ? part_cs : nullptr;
-        p.part_dot = dot ? part_dot : nullptr;
-        p.part_cap = (int)cap;
-        return 0;
-    }
-    // rows / tile_rows: how the route cut the op into tiles (ConvRoute::part_rows, tile_rows)
-    int finish(int Co, int B, long hw, int rows, int tile_rows, hipStream_t s, const char* who) {
-        if (!colsum && !dot) return 0;
-        GIF_REQUIRE(rows > 0 && rows <= cap, "%s: partial-sum rows %d exceed the workspace (%ld)", who, rows, cap);
-        if (colsum)
-            if (int rc = gif::reduce_partials(part_cs, colsum, 1, rows, Co, tmp, s)) return rc;
-        if (dot) {
-            GIF_REQUIRE(tile_rows > 0 && hw % tile_rows == 0 && (long)rows * tile_rows == (long)B * hw,
-                        "%s: dot fusion: tiles of %d rows do not partition the %d samples of %ld pixels", who, tile_rows, B, hw);
-            if (int rc = gif::reduce_partials(part_dot, dot, B, (int)(hw / tile_rows), Co, tmp, s)) return rc;
-        }
-        return 0;
-    }
-};
+// Gradient-producer fusions of one op (common.h FusedSums): carve the partial-sum buffers out of red_ws and check what the direct
+// kernels need (before the launches), reduce them in a fixed order (after).  out_rows = B * Ho * Wo of the op's output.
+int sums_begin(gif::FusedSums& sums, GatherParams& p, const gif_conv_epilogue* e, long out_rows, int Co, long hw, bool single_phase,
+               const char* who) {
+    if (int rc = sums.carve(e, out_rows, Co, who)) return rc;
+    if (!sums.active()) return 0;
+    GIF_REQUIRE(!e->dot || (e->dot_src && single_phase && hw % 256 == 0),
+                "%s: the dot fusion needs dot_src, a single-phase op and a multiple of 256 output pixels per sample (got %ld)", who, hw);
+    p.part_cs = sums.part_cs;
+    p.part_dot = sums.part_dot;
+    p.part_cap = (int)sums.cap;
+    return 0;
+}
+// rows / tile_rows: how the route cut the op into tiles (ConvRoute::part_rows, tile_rows)
+int sums_finish(const gif::FusedSums& sums, int Co, int B, long hw, int rows, int tile_rows, hipStream_t s, const char* who) {
+    if (!sums.active()) return 0;
+    GIF_REQUIRE(rows > 0 && rows <= sums.cap, "%s: partial-sum rows %d exceed the workspace (%ld)", who, rows, sums.cap);
+    GIF_REQUIRE(!sums.dot || (tile_rows > 0 && hw % tile_rows == 0 && (long)rows * tile_rows == (long)B * hw),
+                "%s: dot fusion: tiles of %d rows do not partition the %d samples of %ld pixels", who, tile_rows, B, hw);
+    return sums.reduce(rows, Co, B, sums.dot ? (int)(hw / tile_rows) : 0, s);
+}
 
 // f16x2 launches: the packing is [header: RP row exponents + flag][planes]; the launch gets a fresh gate word (common.h)
 inline int h2_operands(GatherParams& p, int RP, const void* wp2, const void* wp_fallback, hipStream_t s) {
@@ -1851,7 +1790,10 @@ template <typename T>
 int base_params(GatherParams& p, const void* x, const void* wp, void* y, const gif_conv_epilogue* e, int x3, int RP, const void* wp_fallback,
                 hipStream_t s) {
     p.x = x; p.wp = wp; p.y = y; p.x3 = x3;
-    fill_epilogue(p, e);
+    gif::fill_epilogue(p, e);
+    p.in_scale = e ? e->in_scale : nullptr;
+    p.sat_flag = nullptr;
+    p.out_f32 = e ? e->out_f32 : 0;
     if (sizeof(T) == 2) p.sat_flag = gif::f16_sat_flag();
     return x3 == 2 ? h2_operands(p, RP, wp, wp_fallback, s) : 0;
 }
@@ -1859,7 +1801,7 @@ int base_params(GatherParams& p, const void* x, const void* wp, void* y, const g
 // Route and launches of one op over its phases, the guarded bf16x3 twin of an f16x2 op included (a no-op unless the gate was raised), and
 // the reduction of its fused sums.  dims: what the profiling record shows.
 template <typename T>
-int conv_run(const GatherParams& base, const route::ConvPhases& phs, const void* wp_fallback, FusedSums& sums, double flops, int d0, int d3,
+int conv_run(const GatherParams& base, const route::ConvPhases& phs, const void* wp_fallback, const gif::FusedSums& sums, double flops, int d0, int d3,
              int B, long hw, hipStream_t s, const char* who, const char* twin_note) {
     const bool halo_on = halo_switch().load(std::memory_order_relaxed) != 0;
     const route::ConvRoute r = route::conv_route(phs.ph, phs.nph, sizeof(T) == 2, conv_knobs(), halo_on);
@@ -1869,7 +1811,7 @@ int conv_run(const GatherParams& base, const route::ConvPhases& phs, const void*
     if (guarded) {
         for (route::ConvPhase& q : twin.ph) q.x3 = 1;
         r2 = route::conv_route(twin.ph, twin.nph, false, conv_knobs(), halo_on);
-        // FusedSums::finish reduces the per-tile partials through (part_rows, tile_rows): normally those rows were written by the
+        // sums_finish reduces the per-tile partials through (part_rows, tile_rows): normally those rows were written by the
         // f16x2 launch, so the twin must cut the op into the SAME tiles
         if (!r.error && !r2.error && sums.active() && (r2.part_rows != r.part_rows || r2.tile_rows != r.tile_rows)) {
             gif::set_error("%s: the guarded bf16x3 twin tiles the op differently from the f16x2 launch (%d x %d vs %d x %d rows)%s", who,
@@ -1896,7 +1838,7 @@ int conv_run(const GatherParams& base, const route::ConvPhases& phs, const void*
         for (int i = 0; i < r2.nlaunch; ++i)
             if (int rc = conv_dispatch(r2.launch[i], ph, s, who)) return rc;
     }
-    return sums.finish(q0.Co, B, hw, r.part_rows, r.tile_rows, s, who);
+    return sums_finish(sums, q0.Co, B, hw, r.part_rows, r.tile_rows, s, who);
 }
 
 template <typename T>
@@ -1913,8 +1855,8 @@ int conv2d_fwd_impl(const void* big, const void* wp, void* small, const gif_conv
     const route::ConvPhase& q = phs.ph[0];
     GatherParams base{};
     if (int rc = base_params<T>(base, big, wp, small, e, x3, q.RP, wp_fallback, s)) return rc;
-    FusedSums sums;
-    if (int rc = sums.begin(base, e, q.M, q.Co, (long)q.Hp * q.Wp, true, who)) return rc;
+    gif::FusedSums sums;
+    if (int rc = sums_begin(sums, base, e, q.M, q.Co, (long)q.Hp * q.Wp, true, who)) return rc;
     const double flops = 2.0 * q.M * (double)q.Co * q.Ci * q.ntaps;
     if (int rc = conv_run<T>(base, phs, wp_fallback, sums, flops, q.M, q.ntaps * 10 + g->stride, q.B, (long)q.Hp * q.Wp, s, who,
                              ": fused column sums would mix partials"))
@@ -1936,8 +1878,8 @@ int conv2d_bwd_data_impl(const void* small, const void* wp, void* big, const gif
     if (int rc = base_params<T>(base, small, wp, big, e, x3, q.RP, wp_fallback, s)) return rc;
     if (dense)
         if (int rc = check_tapdense(g, e, g->Cs, true, who)) return rc;
-    FusedSums sums;
-    if (int rc = sums.begin(base, e, (long)g->B * g->Hb * g->Wb, q.Co, (long)g->Hb * g->Wb, g->stride == 1, who)) return rc;
+    gif::FusedSums sums;
+    if (int rc = sums_begin(sums, base, e, (long)g->B * g->Hb * g->Wb, q.Co, (long)g->Hb * g->Wb, g->stride == 1, who)) return rc;
     if (phs.need_zero) {  // phases with no tap (e.g. 1x1 stride 2) are zero-filled
         GIF_REQUIRE(!(e && (e->bias || e->residual || e->act || e->mask_src || e->colsum || e->dot)), "%s: epilogue unsupported with empty phases", who);
         hipError_t me = hipMemsetAsync(big, 0, (size_t)g->B * g->Hb * g->Wb * g->Cb * sizeof(T), s);

@@ -7,6 +7,8 @@
 // bulk + remainder split, a merge of phases, the partial-sum rows or the profiling family of these ops.  NOT modelled here, because they
 // are run-time state and sit next to the launch: the zero page, the gate of the guarded twin (GIF_H2_GUARD), the operand pointers and
 // the epilogue.
+// The epilogue fields, the fused column-sum / dot workspace (common.h FusedSums) and the dynamic-LDS launch helper are shared with
+// conv_winograd.hip through conv_common.h; the packed weight operand comes from weight_pack.hip (f16x2: conv_wgrad.hip).
 #pragma once
 #include <stddef.h>
 

@@ -1,4 +1,4 @@
-// fp32 MFMA weight-gradient kernel for gfx950 (NHWC) + weight pack / unpack.
+// fp32 MFMA weight-gradient kernel for gfx950 (NHWC) + unpacking of the gradient (weight PACKING: weight_pack.hip, f16x2 form below).
 //
 // Replaces autograd's wgrad of the F.conv2d / F.conv_transpose2d calls in
 // stylegan2_common_layers.py:176, :330, :339, :345, :405-414.
@@ -12,7 +12,7 @@
 // The per-sample scales implement the wgrad of the modulated convolution (x*s and dy*d) on the fly.
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_common.h"
 #include "wgrad_route.h"  // which kernel a call gets: every tile / stage / twin / family decision of the host code below
 #include "wino_route.h"   // padded dims of the Winograd transforms' outputs
 
@@ -20,8 +20,7 @@ namespace {
 
 namespace route = gif_wgrad;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using gif::f32x16, gif::f32x4, gif::xcd_remap;
 
 struct WgradParams {
     const void* sm;   // small side [B,Hs,Ws,Cs]   (fp32, or f16 for the T = f16 instantiation)
@@ -47,15 +46,6 @@ struct WgradParams {
     // conv_wgrad_h2v2<.., TAPS>: the 128 tile columns hold `tpt` taps x Cb channels (thin big side), `tgroups` column tiles cover the T taps
     int tpt, tgroups;
 };
-
-// XCD-aware, bijective block remap: XCD k (= blockIdx % 8 by dispatch order) gets a contiguous range of logical ids.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int nx = 8;
-    int xcd = bid % nx, idx = bid / nx;
-    int q = nwg / nx, r = nwg % nx;
-    int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
 
 // GLDS = true (no per-sample scales): both operand tiles go global -> LDS directly (global_load_lds_dwordx4, lane-linear
 // destination == the [pixel][channel] tile layout), no staging registers / ds_write; invalid lanes read a zero page.
@@ -952,9 +942,7 @@ template <typename T, int BP, int BQ, int WP_, int WQ_, bool GLDS, int BKP, bool
 void wgrad_launch(dim3 grid, int threads, hipStream_t s, const WgradParams& p) {
     static gif::LdsAttr attr;
     const size_t lds = (size_t)2 * BKP * (BP + BQ) * sizeof(T) + (size_t)(TAB ? p.stab_nb * (BP + BQ) : 0) * sizeof(float);
-    auto kern = conv_wgrad_mfma<T, BP, BQ, WP_, WQ_, GLDS, BKP, TAB, X3>;
-    attr.ensure(reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, p);
+    gif::launch_lds(conv_wgrad_mfma<T, BP, BQ, WP_, WQ_, GLDS, BKP, TAB, X3>, attr, grid, dim3(threads), lds, s, p);
 }
 
 // buffer-addressed DMA of conv_wgrad_h2v2: both operands (per plane in planes mode) within 3.5 GiB; GIF_H2_WGRAD_BUF=0: the 64-bit form (A/B)
@@ -967,14 +955,9 @@ inline bool h2v2_buf_ok(const WgradParams& p) {
 }
 template <bool TAB, bool TAPS>
 inline void wgrad_launch_v2_t(dim3 grid, size_t lds, hipStream_t s, const WgradParams& p) {
-    static gif::LdsAttr attr[2];
-    if (h2v2_buf_ok(p)) {
-        attr[1].ensure(reinterpret_cast<const void*>(conv_wgrad_h2v2<TAB, TAPS, true>), lds);
-        hipLaunchKernelGGL((conv_wgrad_h2v2<TAB, TAPS, true>), grid, dim3(256), lds, s, p);
-    } else {
-        attr[0].ensure(reinterpret_cast<const void*>(conv_wgrad_h2v2<TAB, TAPS, false>), lds);
-        hipLaunchKernelGGL((conv_wgrad_h2v2<TAB, TAPS, false>), grid, dim3(256), lds, s, p);
-    }
+    static gif::LdsAttr attr[2];  // one per kernel: the 64-bit form, the buffer form
+    if (h2v2_buf_ok(p)) gif::launch_lds(conv_wgrad_h2v2<TAB, TAPS, true>, attr[1], grid, dim3(256), lds, s, p);
+    else gif::launch_lds(conv_wgrad_h2v2<TAB, TAPS, false>, attr[0], grid, dim3(256), lds, s, p);
 }
 inline void wgrad_launch_v2(bool tab, dim3 grid, hipStream_t s, const WgradParams& p, bool taps = false) {
     const size_t lds = (size_t)32 * 256 * 4 + (size_t)2 * 256 * 32 * 2 + (size_t)(512 + 8) * 4 + (size_t)(tab ? p.stab_nb * 256 : 0) * sizeof(float);
@@ -983,67 +966,11 @@ inline void wgrad_launch_v2(bool tab, dim3 grid, hipStream_t s, const WgradParam
     else wgrad_launch_v2_t<false, false>(grid, lds, s, p);
 }
 
-template <typename T>
-__global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ wp, int R, int C, int KH,
-                                   int KW, int RP, int CP, long sr, long sc, long sky, long skx, float scale) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = (long)KH * KW * RP * CP;
-    if (idx >= total) return;
-    int c = (int)(idx % CP);
-    long rest = idx / CP;
-    int r = (int)(rest % RP);
-    int t = (int)(rest / RP);
-    int ky = t / KW, kx = t - ky * KW;
-    float v = 0.f;
-    if (r < R && c < C) v = scale * w[r * sr + c * sc + ky * sky + kx * skx];
-    wp[idx] = (T)v;
-}
-
-// bf16x3 packing: wp3[t][term][r][c] (bf16 bits) = term-th part of the exact three-way split of scale * w
-__global__ void pack_weight_x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp3, int R, int C, int KH,
-                                      int KW, int RP, int CP, long sr, long sc, long sky, long skx, float scale) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = (long)KH * KW * RP * CP;
-    if (idx >= total) return;
-    int c = (int)(idx % CP);
-    long rest = idx / CP;
-    int r = (int)(rest % RP);
-    int t = (int)(rest / RP);
-    int ky = t / KW, kx = t - ky * KW;
-    float v = 0.f;
-    if (r < R && c < C) v = scale * w[r * sr + c * sc + ky * sky + kx * skx];
-    unsigned h, m, l;
-    gif::split_pair(v, 0.f, h, m, l);
-    const size_t plane = (size_t)RP * CP;
-    unsigned short* o = wp3 + (size_t)t * 3 * plane + (size_t)r * CP + c;
-    o[0] = (unsigned short)(h & 0xffffu);
-    o[plane] = (unsigned short)(m & 0xffffu);
-    o[2 * plane] = (unsigned short)(l & 0xffffu);
-}
-
-// tap-dense variant (3x3): wp3[step][term][r][32], K order (tap, channel) without per-tap padding
-__global__ void pack_weight_x3_dense_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp3, int R, int C, int cpt,
-                                            int steps, int RP, long sr, long sc, long sky, long skx, float scale) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = (long)steps * RP * 32;
-    if (idx >= total) return;
-    const int k = (int)(idx % 32);
-    const long rest = idx / 32;
-    const int r = (int)(rest % RP);
-    const int st = (int)(rest / RP);
-    const int q = st * 8 + k / 4;
-    const int t = q / cpt, c = (q - t * cpt) * 4 + k % 4;
-    float v = 0.f;
-    if (t < 9 && r < R && c < C) v = scale * w[r * sr + c * sc + (t / 3) * sky + (t % 3) * skx];
-    unsigned h, m, l;
-    gif::split_pair(v, 0.f, h, m, l);
-    const size_t plane = (size_t)RP * 32;
-    unsigned short* o = wp3 + (size_t)st * 3 * plane + (size_t)r * 32 + k;
-    o[0] = (unsigned short)(h & 0xffffu);
-    o[plane] = (unsigned short)(m & 0xffffu);
-    o[2 * plane] = (unsigned short)(l & 0xffffu);
-}
-
+// ---- f16x2 weight PACKING (operand of the forward and data-gradient kernels of conv_igemm.hip; the other packings: weight_pack.hip).
+// It is in this translation unit for its device code's sake: gif::h2_exp_for is specialised per translation unit by the targets its callers
+// pass (hipcc internalises device functions and propagates their arguments before inlining).  Here those are kH2TargetW (this kernel)
+// and kH2Target (the f16x2 weight-gradient kernels); with either alone the clamp compiles to other instructions, in this kernel and in
+// nine weight-gradient kernels (conv_wgrad_h2v2: + 2 VGPRs).
 // f16x2 packing (common.h "h2"): one workgroup per packed row.  Header hdr[r] = the row's exponent e (row maximum over all taps and
 // channels of scale * w lands in [2^14, 2^15)), hdr[RP + r] = the row's flag; planes wp2[t][2][RP][CP] (f16 bits) = hi / lo of
 // scale * w * 2^e.  A 16-channel K group (the kernels' k-groups: 16 consecutive padded channels of one tap) whose maximum lies more
@@ -1158,8 +1085,6 @@ __global__ void unpack_wgrad_kernel(const float* __restrict__ ws, float* __restr
 // 1024-thread workgroups: 16 waves share a pixel range; their accumulators are reduced through LDS in a fixed order and
 // written as one split of the usual [split][tap][RP][CP] workspace (deterministic, same unpack kernel).
 // ------------------------------------------------------------------------------------------------------------------
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 struct SmallWgradParams {
     const float* sm;  // gy [B,H,W,Cs]
     const float* bg;  // x  [B,H,W,Cb]
@@ -1175,11 +1100,11 @@ __global__ void __launch_bounds__(1024) conv_wgrad_small_mfma(const SmallWgradPa
     const long n_begin = (long)blockIdx.x * p.chunk;
     long n_end = n_begin + p.chunk;
     if (n_end > p.Ntot) n_end = p.Ntot;
-    f32x4v acc[9][2];
+    f32x4 acc[9][2];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) acc[t][ct] = (f32x4v)(0.f);
+        for (int ct = 0; ct < 2; ++ct) acc[t][ct] = (f32x4)(0.f);
     const bool cin_ok = c < p.Cb;
     const bool co_ok[2] = {c < p.Cs, 16 + c < p.Cs};
     // this lane's pixel: n = n_begin + (quad index)*4 + k ; waves take quads round-robin (16 waves => +64 pixels per step)
@@ -1236,7 +1161,7 @@ __global__ void __launch_bounds__(1024) conv_wgrad_small_mfma(const SmallWgradPa
             for (int t = 0; t < 9; ++t)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct)
-                    *reinterpret_cast<f32x4v*>(dst + (t * 2 + ct) * 256 + lane * 4) = acc[t][ct];
+                    *reinterpret_cast<f32x4*>(dst + (t * 2 + ct) * 256 + lane * 4) = acc[t][ct];
         }
         __syncthreads();
         if (wave < h) {
@@ -1245,7 +1170,7 @@ __global__ void __launch_bounds__(1024) conv_wgrad_small_mfma(const SmallWgradPa
             for (int t = 0; t < 9; ++t)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct)
-                    acc[t][ct] += *reinterpret_cast<const f32x4v*>(src + (t * 2 + ct) * 256 + lane * 4);
+                    acc[t][ct] += *reinterpret_cast<const f32x4*>(src + (t * 2 + ct) * 256 + lane * 4);
         }
         __syncthreads();
     }
@@ -1510,7 +1435,7 @@ __global__ void wino_unpack_wgrad_kernel(const float* __restrict__ ws, float* __
 route::WgradKnobs wgrad_knobs() {
     static const route::WgradKnobs once = [] {
         route::WgradKnobs k;
-        const auto num = [](const char* name, int unset) { const char* e = gif::knob(name); return e ? atoi(e) : unset; };
+        const auto num = gif::knob_int;
         k.x3_wgrad_thin = num("GIF_X3_WGRAD_THIN", k.x3_wgrad_thin);
         k.x3_wgrad_simple = num("GIF_X3_WGRAD_SIMPLE", 0) != 0;
         k.h2_wgrad_plain_tab = num("GIF_H2_WGRAD_PLAIN_TAB", 1) != 0;
@@ -1609,28 +1534,100 @@ int wgrad_dispatch(const route::WgradRoute& r, int nsplit, hipStream_t s, WgradP
     return 0;
 }
 
+// The f16x2 packings, one launch each: header and planes behind wp2; wp3 != NULL: the bf16x3 packing of the same weights as well;
+// steps > 0: the tap-dense K order (`steps` K steps of CP = 32 floats, cpt 16-byte chunks per tap) instead of KH * KW taps of CP channels.
+// The entry points have validated their arguments.
+int pack_h2(const char* who, const float* w, void* wp2, void* wp3, int R, int C, int KH, int KW, int RP, int CP, int64_t sr, int64_t sc,
+            int64_t sky, int64_t skx, float scale, int cpt, int steps, gif_stream_t stream) {
+    int* hdr = static_cast<int*>(wp2);
+    unsigned short* planes = reinterpret_cast<unsigned short*>(static_cast<char*>(wp2) + gif::h2_header_bytes(RP));
+    const int T = steps ? steps : KH * KW;
+    const size_t lds = (size_t)T * CP * sizeof(float);  // (tap-dense: <= 8 steps of 32 floats, always fits)
+    GIF_REQUIRE(lds <= 64 * 1024, "%s: a row of %d x %d values does not fit the staging LDS", who, T, CP);
+    pack_weight_h2_kernel<<<RP, 256, lds, gif::as_stream(stream)>>>(w, hdr, planes, static_cast<unsigned short*>(wp3), R, C, KH, KW, RP, CP, sr,
+                                                                    sc, sky, skx, scale, cpt, steps);
+    return gif::check_launch(who);
+}
+
+// everything of WgradParams but the per-launch fields (wgrad_dispatch, wgrad_launch_one), from the geometry, the route and the pointers
+WgradParams wgrad_params(const route::WgradShape& g, const route::WgradRoute& r, const void* small, const void* big, float* ws,
+                         const float* small_scale, const float* big_scale, const void* zero) {
+    WgradParams p{};
+    p.sm = small; p.bg = big; p.ws = ws; p.ss = small_scale; p.bs = big_scale;
+    p.B = g.B; p.Hs = g.Hs; p.Ws = g.Ws; p.Cs = g.Cs; p.Hb = g.Hb; p.Wb = g.Wb; p.Cb = g.Cb;
+    p.KW = g.KW; p.stride = g.stride; p.pad = g.pad; p.T = g.KH * g.KW;
+    p.RP = r.RP; p.CP = r.CP; p.Ntot = route::wgrad_ntot(g); p.chunk = r.chunk;
+    p.tiles_q = r.tiles_q; p.tiles_pq = r.tiles_pq; p.stab_nb = r.stab_nb; p.zero = zero;
+    return p;
+}
+
+// The direct weight gradient behind gif_conv2d_wgrad_f32 / _f32x3 / _f32h2 (T = float; mode: 0 native fp32 MFMA, 1 bf16x3, 2 f16x2 with
+// the guarded bf16x3 fallback — launch shapes f16x2 is not built for run bf16x3) and gif_conv2d_wgrad_f16 (T = f16: square tiles on the
+// LDS-DMA kernel, wgrad_route_f16; fp32 partial sums, the same unpack kernel; mode unused).
+template <typename T>
+int conv2d_wgrad_impl(const void* small, const void* big, float* ws, const float* small_scale, const float* big_scale, const gif_conv_geom* g,
+                      int nsplit, gif_stream_t stream, int mode) {
+    constexpr bool F16 = sizeof(T) == 2;
+    constexpr int CMULT = F16 ? 8 : 4;  // channels per 16-byte DMA chunk
+    const char* const who = F16 ? "conv2d_wgrad_f16" : "conv2d_wgrad";
+    GIF_REQUIRE(g && small && big && ws && nsplit >= 1, "%s: bad arguments", who);
+    GIF_REQUIRE(g->Cb % CMULT == 0 && g->Cs % CMULT == 0, "%s: channels must be multiples of %d", who, CMULT);
+    GIF_REQUIRE(g->KH >= 1 && g->KH <= 3 && g->KW >= 1 && g->KW <= 3 && (g->stride == 1 || g->stride == 2), "%s: unsupported kernel/stride", who);
+    GIF_REQUIRE((long)g->B * g->Hs * g->Ws * g->Cs < (1L << 31) && (long)g->B * g->Hb * g->Wb * g->Cb < (1L << 31),
+                "%s: tensors of >= 2^31 elements are not supported (32-bit offsets)", who);
+    const bool scaled = small_scale || big_scale;
+    const route::WgradShape sh = wgrad_shape(g, scaled);
+    const route::WgradRoute r = F16 ? route::wgrad_route_f16(sh, nsplit, wgrad_knobs()) : route::wgrad_route(sh, mode, nsplit, wgrad_knobs());
+    hipStream_t s = gif::as_stream(stream);
+    const int T9 = g->KH * g->KW;
+    const long Ntot = route::wgrad_ntot(sh);
+    const double flops = 2.0 * Ntot * (double)g->Cs * g->Cb * T9;
+    const void* zero = gif::zero_page16();
+    GIF_REQUIRE(zero, "%s: zero page lookup failed", who);
+    gif::ProfScope prof(r.family, flops, s, (int)Ntot, g->Cs, g->Cb, T9 * 10 + g->stride + (scaled ? 100 : 0));
+    const dim3 grid((unsigned)(r.primary.wgs_per_split * nsplit)), block(r.primary.threads);
+    // the two kernels outside the tiled ladder: each exists for one element type only
+    if constexpr (F16) {
+        if (r.primary.kernel == route::WGRAD_HALO) {
+            HaloWgradParams q{};
+            q.sm = small; q.bg = big; q.ws = ws; q.ss = small_scale; q.bs = big_scale;
+            q.B = g->B; q.Hs = g->Hs; q.Ws = g->Ws; q.Hb = g->Hb; q.Wb = g->Wb; q.Cs = g->Cs; q.Cb = g->Cb;
+            q.KH = g->KH; q.KW = g->KW; q.pad = g->pad;
+            q.tiles_x = gif::cdiv(g->Ws, 16); q.tiles_y = gif::cdiv(g->Hs, 16); q.ntiles = g->B * q.tiles_x * q.tiles_y;
+            q.zero = zero;
+            const size_t lds = (size_t)2 * kHwBufHalfs * sizeof(gif::f16);
+            static gif::LdsAttr attr, attr_tr;
+            if (!r.primary.TR) gif::launch_lds(conv_wgrad_halo_f16<false>, attr, grid, block, lds, s, q);
+            else gif::launch_lds(conv_wgrad_halo_f16<true>, attr_tr, grid, block, lds, s, q);
+            return gif::check_launch("conv2d_wgrad_f16(halo)");
+        }
+    } else {
+        if (r.primary.kernel == route::WGRAD_SMALL) {
+            SmallWgradParams q{};
+            q.sm = static_cast<const float*>(small); q.bg = static_cast<const float*>(big); q.ws = ws;
+            q.B = g->B; q.H = g->Hs; q.W = g->Ws; q.Cs = g->Cs; q.Cb = g->Cb; q.RP = r.RP; q.CP = r.CP;
+            q.Ntot = Ntot; q.chunk = r.chunk;
+            static gif::LdsAttr attr;
+            gif::launch_lds(conv_wgrad_small_mfma, attr, grid, block, (size_t)8 * 18 * 256 * sizeof(float), s, q);
+            return gif::check_launch("conv2d_wgrad(small)");
+        }
+    }
+    const WgradParams p = wgrad_params(sh, r, small, big, ws, small_scale, big_scale, zero);
+    if constexpr (F16) {
+        if (scaled) {
+            // the scale table is indexed per stage: a stage must not straddle two samples
+            const long HWs = (long)g->Hs * g->Ws;
+            GIF_REQUIRE((size_t)r.stab_nb * 2 * r.tile_f16 * sizeof(float) <= 64 * 1024, "conv2d_wgrad_f16: scale table too large");
+            GIF_REQUIRE(HWs % 16 == 0, "conv2d_wgrad_f16: modulated weight gradient needs Hs*Ws %% 16 == 0 (got %ld)", HWs);
+        }
+    }
+    if (int rc = wgrad_dispatch(r, nsplit, s, p)) return rc;
+    return gif::check_launch(who);
+}
+
 }  // namespace
 
 extern "C" {
-
-int gif_pack_weight_f32(const float* w, float* wp, int R, int C, int KH, int KW, int RP, int CP, int64_t sr,
-                        int64_t sc, int64_t sky, int64_t skx, float scale, gif_stream_t stream) {
-    GIF_REQUIRE(w && wp && R > 0 && C > 0 && RP >= R && CP >= C && KH > 0 && KW > 0, "pack_weight: bad arguments");
-    long total = (long)KH * KW * RP * CP;
-    pack_weight_kernel<float><<<gif::cdiv(total, 256), 256, 0, gif::as_stream(stream)>>>(w, wp, R, C, KH, KW, RP, CP, sr, sc,
-                                                                                           sky, skx, scale);
-    return gif::check_launch("pack_weight");
-}
-
-/* fp32 master weights -> f16 packed operand of the f16 convolution kernels (same [tap][RP][CP] layout) */
-int gif_pack_weight_f32x3(const float* w, void* wp3, int R, int C, int KH, int KW, int RP, int CP, int64_t sr, int64_t sc,
-                          int64_t sky, int64_t skx, float scale, gif_stream_t stream) {
-    GIF_REQUIRE(w && wp3 && R > 0 && C > 0 && RP >= R && CP >= C && KH > 0 && KW > 0, "pack_weight_f32x3: bad arguments");
-    long total = (long)KH * KW * RP * CP;
-    pack_weight_x3_kernel<<<gif::cdiv(total, 256), 256, 0, gif::as_stream(stream)>>>(w, static_cast<unsigned short*>(wp3), R, C,
-                                                                                       KH, KW, RP, CP, sr, sc, sky, skx, scale);
-    return gif::check_launch("pack_weight_f32x3");
-}
 
 /* f16x2 packing: [RP int32 row exponents][RP int32 row flags][tap][2][RP][CP] f16 — gif_pack_weight_f32h2_bytes of device memory */
 int64_t gif_pack_weight_f32h2_bytes(int KH, int KW, int RP, int CP) {
@@ -1642,12 +1639,7 @@ int gif_pack_weight_f32h2(const float* w, void* wp2, int R, int C, int KH, int K
                           int64_t sky, int64_t skx, float scale, gif_stream_t stream) {
     GIF_REQUIRE(w && wp2 && R > 0 && C > 0 && RP >= R && CP >= C && KH > 0 && KW > 0 && RP % 32 == 0 && CP % 32 == 0,
                 "pack_weight_f32h2: bad arguments");
-    int* hdr = static_cast<int*>(wp2);
-    unsigned short* planes = reinterpret_cast<unsigned short*>(static_cast<char*>(wp2) + gif::h2_header_bytes(RP));
-    const size_t lds = (size_t)KH * KW * CP * sizeof(float);
-    GIF_REQUIRE(lds <= 64 * 1024, "pack_weight_f32h2: a row of %d x %d values does not fit the staging LDS", KH * KW, CP);
-    pack_weight_h2_kernel<<<RP, 256, lds, gif::as_stream(stream)>>>(w, hdr, planes, nullptr, R, C, KH, KW, RP, CP, sr, sc, sky, skx, scale, 0, 0);
-    return gif::check_launch("pack_weight_f32h2");
+    return pack_h2("pack_weight_f32h2", w, wp2, nullptr, R, C, KH, KW, RP, CP, sr, sc, sky, skx, scale, 0, 0, stream);
 }
 
 /* both packings of the same weights in ONE launch: wp2 (f16x2, as gif_pack_weight_f32h2) and wp3 (bf16x3, as gif_pack_weight_f32x3) */
@@ -1655,13 +1647,7 @@ int gif_pack_weight_f32h2x3(const float* w, void* wp2, void* wp3, int R, int C, 
                             int64_t sky, int64_t skx, float scale, gif_stream_t stream) {
     GIF_REQUIRE(w && wp2 && wp3 && R > 0 && C > 0 && RP >= R && CP >= C && KH > 0 && KW > 0 && RP % 32 == 0 && CP % 32 == 0,
                 "pack_weight_f32h2x3: bad arguments");
-    int* hdr = static_cast<int*>(wp2);
-    unsigned short* planes = reinterpret_cast<unsigned short*>(static_cast<char*>(wp2) + gif::h2_header_bytes(RP));
-    const size_t lds = (size_t)KH * KW * CP * sizeof(float);
-    GIF_REQUIRE(lds <= 64 * 1024, "pack_weight_f32h2x3: a row of %d x %d values does not fit the staging LDS", KH * KW, CP);
-    pack_weight_h2_kernel<<<RP, 256, lds, gif::as_stream(stream)>>>(w, hdr, planes, static_cast<unsigned short*>(wp3), R, C, KH, KW, RP, CP, sr,
-                                                                    sc, sky, skx, scale, 0, 0);
-    return gif::check_launch("pack_weight_f32h2x3");
+    return pack_h2("pack_weight_f32h2x3", w, wp2, wp3, R, C, KH, KW, RP, CP, sr, sc, sky, skx, scale, 0, 0, stream);
 }
 
 /* tap-dense K order (gif_conv2d_x3_tapdense_steps): wp2 = [2 RP int32 header][steps][2][RP][32] f16, wp3 = [steps][3][RP][32] bf16 (as
@@ -1677,39 +1663,7 @@ int gif_pack_weight_f32h2x3_tapdense(const float* w, void* wp2, void* wp3, int R
     const int steps = gif_conv2d_x3_tapdense_steps(cin_act, KH, KW);
     GIF_REQUIRE(w && wp2 && wp3 && R > 0 && C > 0 && RP >= R && RP % 32 == 0 && cin_act >= C && steps > 0,
                 "pack_weight_f32h2x3_tapdense: bad arguments");
-    int* hdr = static_cast<int*>(wp2);
-    unsigned short* planes = reinterpret_cast<unsigned short*>(static_cast<char*>(wp2) + gif::h2_header_bytes(RP));
-    const size_t lds = (size_t)steps * 32 * sizeof(float);
-    pack_weight_h2_kernel<<<RP, 256, lds, gif::as_stream(stream)>>>(w, hdr, planes, static_cast<unsigned short*>(wp3), R, C, KH, KW, RP, 32, sr,
-                                                                    sc, sky, skx, scale, cin_act / 4, steps);
-    return gif::check_launch("pack_weight_f32h2x3_tapdense");
-}
-
-/* K steps (32-float chunks) of the tap-dense order, or 0 if the mode does not apply: 3x3 kernels, 8 <= cin_act < 32, cin_act % 4 == 0 */
-int gif_conv2d_x3_tapdense_steps(int cin_act, int KH, int KW) {
-    if (KH != 3 || KW != 3 || cin_act < 8 || cin_act >= 32 || cin_act % 4 != 0) return 0;
-    return (9 * (cin_act / 4) + 7) / 8;
-}
-
-/* wp3[step][term][RP][32] (bf16 bits): element k of step s is float k % 4 of 16-byte chunk q = 8 s + k / 4, i.e. tap q / (cin_act/4),
- * channel 4 (q % (cin_act/4)) + k % 4 — the order in which the tap-dense kernels walk K (conv_igemm.hip, GatherParams::dense) */
-int gif_pack_weight_f32x3_tapdense(const float* w, void* wp3, int R, int C, int cin_act, int KH, int KW, int RP, int64_t sr, int64_t sc,
-                                   int64_t sky, int64_t skx, float scale, gif_stream_t stream) {
-    const int steps = gif_conv2d_x3_tapdense_steps(cin_act, KH, KW);
-    GIF_REQUIRE(w && wp3 && R > 0 && C > 0 && RP >= R && cin_act >= C && steps > 0, "pack_weight_f32x3_tapdense: bad arguments");
-    long total = (long)steps * RP * 32;
-    pack_weight_x3_dense_kernel<<<gif::cdiv(total, 256), 256, 0, gif::as_stream(stream)>>>(w, static_cast<unsigned short*>(wp3), R, C,
-                                                                                             cin_act / 4, steps, RP, sr, sc, sky, skx, scale);
-    return gif::check_launch("pack_weight_f32x3_tapdense");
-}
-
-int gif_pack_weight_f16(const float* w, void* wp, int R, int C, int KH, int KW, int RP, int CP, int64_t sr, int64_t sc,
-                        int64_t sky, int64_t skx, float scale, gif_stream_t stream) {
-    GIF_REQUIRE(w && wp && R > 0 && C > 0 && RP >= R && CP >= C && KH > 0 && KW > 0, "pack_weight_f16: bad arguments");
-    long total = (long)KH * KW * RP * CP;
-    pack_weight_kernel<gif::f16><<<gif::cdiv(total, 256), 256, 0, gif::as_stream(stream)>>>(w, static_cast<gif::f16*>(wp), R, C, KH,
-                                                                                              KW, RP, CP, sr, sc, sky, skx, scale);
-    return gif::check_launch("pack_weight_f16");
+    return pack_h2("pack_weight_f32h2x3_tapdense", w, wp2, wp3, R, C, KH, KW, RP, 32, sr, sc, sky, skx, scale, cin_act / 4, steps, stream);
 }
 
 /* ---- f16 operands (BASELINE config 5): square tiles on the LDS-DMA kernel (wgrad_route.h: wgrad_route_f16), fp32 partial sums, the
@@ -1727,56 +1681,7 @@ int gif_conv2d_wgrad_splits_f16(const gif_conv_geom* g) {
 
 int gif_conv2d_wgrad_f16(const void* small, const void* big, float* ws, const float* small_scale, const float* big_scale,
                          const gif_conv_geom* g, int nsplit, gif_stream_t stream) {
-    GIF_REQUIRE(g && small && big && ws && nsplit >= 1, "conv2d_wgrad_f16: bad arguments");
-    GIF_REQUIRE(g->Cb % 8 == 0 && g->Cs % 8 == 0, "conv2d_wgrad_f16: channels must be multiples of 8");
-    GIF_REQUIRE(g->KH >= 1 && g->KH <= 3 && g->KW >= 1 && g->KW <= 3 && (g->stride == 1 || g->stride == 2),
-                "conv2d_wgrad_f16: unsupported kernel/stride");
-    GIF_REQUIRE((long)g->B * g->Hs * g->Ws * g->Cs < (1L << 31) && (long)g->B * g->Hb * g->Wb * g->Cb < (1L << 31),
-                "conv2d_wgrad_f16: tensors of >= 2^31 elements are not supported (32-bit offsets)");
-    const bool scaled = small_scale || big_scale;
-    const route::WgradRoute r = route::wgrad_route_f16(wgrad_shape(g, scaled), nsplit, wgrad_knobs());
-    hipStream_t s = gif::as_stream(stream);
-    const int T = g->KH * g->KW;
-    const long Ntot = (long)g->B * g->Hs * g->Ws;
-    const double flops = 2.0 * Ntot * (double)g->Cs * g->Cb * T;
-    const void* zero = gif::zero_page16();
-    GIF_REQUIRE(zero, "conv2d_wgrad_f16: zero page lookup failed");
-    if (r.primary.kernel == route::WGRAD_HALO) {
-        HaloWgradParams q{};
-        q.sm = small; q.bg = big; q.ws = ws; q.ss = small_scale; q.bs = big_scale;
-        q.B = g->B; q.Hs = g->Hs; q.Ws = g->Ws; q.Hb = g->Hb; q.Wb = g->Wb; q.Cs = g->Cs; q.Cb = g->Cb;
-        q.KH = g->KH; q.KW = g->KW; q.pad = g->pad;
-        q.tiles_x = gif::cdiv(g->Ws, 16); q.tiles_y = gif::cdiv(g->Hs, 16); q.ntiles = g->B * q.tiles_x * q.tiles_y;
-        q.zero = zero;
-        gif::ProfScope prof(r.family, flops, s, (int)Ntot, g->Cs, g->Cb, T * 10 + g->stride + (scaled ? 100 : 0));
-        const size_t lds = (size_t)2 * kHwBufHalfs * sizeof(gif::f16);
-        const dim3 grid((unsigned)(r.primary.wgs_per_split * nsplit));
-        if (!r.primary.TR) {
-            static gif::LdsAttr attr;
-            attr.ensure(reinterpret_cast<const void*>(conv_wgrad_halo_f16<false>), lds);
-            hipLaunchKernelGGL(conv_wgrad_halo_f16<false>, grid, dim3(r.primary.threads), lds, s, q);
-        } else {
-            static gif::LdsAttr attr_tr;
-            attr_tr.ensure(reinterpret_cast<const void*>(conv_wgrad_halo_f16<true>), lds);
-            hipLaunchKernelGGL(conv_wgrad_halo_f16<true>, grid, dim3(r.primary.threads), lds, s, q);
-        }
-        return gif::check_launch("conv2d_wgrad_f16(halo)");
-    }
-    WgradParams p{};
-    p.sm = small; p.bg = big; p.ws = ws; p.ss = small_scale; p.bs = big_scale;
-    p.B = g->B; p.Hs = g->Hs; p.Ws = g->Ws; p.Cs = g->Cs; p.Hb = g->Hb; p.Wb = g->Wb; p.Cb = g->Cb;
-    p.KW = g->KW; p.stride = g->stride; p.pad = g->pad; p.T = T;
-    p.RP = r.RP; p.CP = r.CP; p.Ntot = Ntot; p.chunk = r.chunk;
-    p.tiles_q = r.tiles_q; p.tiles_pq = r.tiles_pq; p.stab_nb = r.stab_nb; p.zero = zero;
-    gif::ProfScope prof(r.family, flops, s, (int)Ntot, g->Cs, g->Cb, T * 10 + g->stride + (scaled ? 100 : 0));
-    if (scaled) {
-        // the scale table is indexed per stage: a stage must not straddle two samples
-        const long HWs = (long)g->Hs * g->Ws;
-        GIF_REQUIRE((size_t)r.stab_nb * 2 * r.tile_f16 * sizeof(float) <= 64 * 1024, "conv2d_wgrad_f16: scale table too large");
-        GIF_REQUIRE(HWs % 16 == 0, "conv2d_wgrad_f16: modulated weight gradient needs Hs*Ws %% 16 == 0 (got %ld)", HWs);
-    }
-    if (int rc = wgrad_dispatch(r, nsplit, s, p)) return rc;
-    return gif::check_launch("conv2d_wgrad_f16");
+    return conv2d_wgrad_impl<gif::f16>(small, big, ws, small_scale, big_scale, g, nsplit, stream, 0);
 }
 
 int gif_conv2d_wgrad_dims(int Cs, int Cb, int* RP, int* CP) {
@@ -1795,59 +1700,20 @@ int gif_conv2d_wgrad_splits(const gif_conv_geom* g) {
     return route::wgrad_splits(sh, mode, k);
 }
 
-// mode: 0 native fp32 MFMA, 1 bf16x3, 2 f16x2 with the guarded bf16x3 fallback (launch shapes f16x2 is not built for run bf16x3)
-static int conv2d_wgrad_f32_impl(const float* small, const float* big, float* ws, const float* small_scale,
-                                 const float* big_scale, const gif_conv_geom* g, int nsplit, gif_stream_t stream, int mode) {
-    GIF_REQUIRE(g && small && big && ws && nsplit >= 1, "conv2d_wgrad: bad arguments");
-    GIF_REQUIRE(g->Cb % 4 == 0 && g->Cs % 4 == 0, "conv2d_wgrad: channels must be multiples of 4");
-    GIF_REQUIRE(g->KH >= 1 && g->KH <= 3 && g->KW >= 1 && g->KW <= 3 && (g->stride == 1 || g->stride == 2),
-                "conv2d_wgrad: unsupported kernel/stride");
-    GIF_REQUIRE((long)g->B * g->Hs * g->Ws * g->Cs < (1L << 31) && (long)g->B * g->Hb * g->Wb * g->Cb < (1L << 31),
-                "conv2d_wgrad: tensors of >= 2^31 elements are not supported (32-bit offsets)");
-    const bool scaled = small_scale || big_scale;
-    const route::WgradRoute r = route::wgrad_route(wgrad_shape(g, scaled), mode, nsplit, wgrad_knobs());
-    hipStream_t s = gif::as_stream(stream);
-    const int T = g->KH * g->KW;
-    const long Ntot = (long)g->B * g->Hs * g->Ws;
-    const double flops = 2.0 * Ntot * (double)g->Cs * g->Cb * T;
-    const void* zero = gif::zero_page16();
-    GIF_REQUIRE(zero, "conv2d_wgrad: zero page lookup failed");
-    gif::ProfScope prof(r.family, flops, s, (int)Ntot, g->Cs, g->Cb, T * 10 + g->stride + (scaled ? 100 : 0));
-    if (r.primary.kernel == route::WGRAD_SMALL) {
-        SmallWgradParams q{};
-        q.sm = small; q.bg = big; q.ws = ws;
-        q.B = g->B; q.H = g->Hs; q.W = g->Ws; q.Cs = g->Cs; q.Cb = g->Cb; q.RP = r.RP; q.CP = r.CP;
-        q.Ntot = Ntot; q.chunk = r.chunk;
-        const size_t lds = (size_t)8 * 18 * 256 * sizeof(float);
-        static gif::LdsAttr attr;
-        attr.ensure(reinterpret_cast<const void*>(conv_wgrad_small_mfma), lds);
-        hipLaunchKernelGGL(conv_wgrad_small_mfma, dim3((unsigned)(r.primary.wgs_per_split * nsplit)), dim3(r.primary.threads), lds, s, q);
-        return gif::check_launch("conv2d_wgrad(small)");
-    }
-    WgradParams p{};
-    p.sm = small; p.bg = big; p.ws = ws; p.ss = small_scale; p.bs = big_scale;
-    p.B = g->B; p.Hs = g->Hs; p.Ws = g->Ws; p.Cs = g->Cs; p.Hb = g->Hb; p.Wb = g->Wb; p.Cb = g->Cb;
-    p.KW = g->KW; p.stride = g->stride; p.pad = g->pad; p.T = T;
-    p.RP = r.RP; p.CP = r.CP; p.Ntot = Ntot; p.chunk = r.chunk;
-    p.tiles_q = r.tiles_q; p.tiles_pq = r.tiles_pq; p.stab_nb = r.stab_nb; p.zero = zero;
-    if (int rc = wgrad_dispatch(r, nsplit, s, p)) return rc;
-    return gif::check_launch("conv2d_wgrad");
-}
-
 int gif_conv2d_wgrad_f32(const float* small, const float* big, float* ws, const float* small_scale,
                          const float* big_scale, const gif_conv_geom* g, int nsplit, gif_stream_t stream) {
-    return conv2d_wgrad_f32_impl(small, big, ws, small_scale, big_scale, g, nsplit, stream, 0);
+    return conv2d_wgrad_impl<float>(small, big, ws, small_scale, big_scale, g, nsplit, stream, 0);
 }
 
 int gif_conv2d_wgrad_f32x3(const float* small, const float* big, float* ws, const float* small_scale,
                            const float* big_scale, const gif_conv_geom* g, int nsplit, gif_stream_t stream) {
-    return conv2d_wgrad_f32_impl(small, big, ws, small_scale, big_scale, g, nsplit, stream, 1);
+    return conv2d_wgrad_impl<float>(small, big, ws, small_scale, big_scale, g, nsplit, stream, 1);
 }
 
 /* f16x2 (ABI 4): same contract; the f16x2 launch is followed by its guarded bf16x3 twin (a no-op unless the gate was raised) */
 int gif_conv2d_wgrad_f32h2(const float* small, const float* big, float* ws, const float* small_scale,
                            const float* big_scale, const gif_conv_geom* g, int nsplit, gif_stream_t stream) {
-    return conv2d_wgrad_f32_impl(small, big, ws, small_scale, big_scale, g, nsplit, stream, 2);
+    return conv2d_wgrad_impl<float>(small, big, ws, small_scale, big_scale, g, nsplit, stream, 2);
 }
 
 int gif_unpack_wgrad_f32(const float* ws, float* dw, int nsplit, int R, int C, int KH, int KW, int RP, int CP,
@@ -1891,16 +1757,12 @@ static int conv3x3_winograd_wgrad_impl(const float* x, const float* gy, float* V
     const route::WgradShape planes{1, 1, (int)ntiles, CbP, 1, (int)ntiles, CsP, 1, 1, 1, 0, false, true};
     const route::WgradRoute r = route::wgrad_route(planes, mode, nsplit, wgrad_knobs());
     gif::ProfScope prof(r.family, flops, s, (int)((long)B * H * W), Cs, Cb, 1091 + (small_scale || big_scale ? 100 : 0));
-    WgradParams p{};
-    p.sm = Mg; p.bg = V; p.ws = ws; p.ss = nullptr; p.bs = nullptr;
-    p.B = 1; p.Hs = 1; p.Ws = (int)ntiles; p.Cs = CsP; p.Hb = 1; p.Wb = (int)ntiles; p.Cb = CbP;
-    p.KW = 1; p.stride = 1; p.pad = 0; p.T = 16;
+    const void* zero = gif::zero_page16();
+    GIF_REQUIRE(zero, "winograd_wgrad: zero page lookup failed");
+    WgradParams p = wgrad_params(planes, r, Mg, V, ws, nullptr, nullptr, zero);
+    p.T = 16;
     p.sm_plane = ntiles_pad * CsP;
     p.bg_plane = ntiles_pad * CbP;
-    p.RP = r.RP; p.CP = r.CP; p.Ntot = ntiles; p.chunk = r.chunk;
-    p.tiles_q = r.tiles_q; p.tiles_pq = r.tiles_pq; p.stab_nb = r.stab_nb;
-    p.zero = gif::zero_page16();
-    GIF_REQUIRE(p.zero, "winograd_wgrad: zero page lookup failed");
     if (int rc = wgrad_dispatch(r, nsplit, s, p)) return rc;
     return gif::check_launch("conv3x3_winograd_wgrad");
 }

@@ -18,23 +18,14 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.h"
+#include "conv_common.h"
 #include "wino_route.h"  // which kernels a call gets and every padded size: every decision of the host code below
 
 namespace route = gif_wino;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int nx = 8;
-    int xcd = bid % nx, idx = bid / nx;
-    int q = nwg / nx, r = nwg % nx;
-    int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
+using gif::f32x16, gif::f32x4, gif::xcd_remap;
 
 // GEMM tile: 256 threads = 4 waves as 2 (M) x 2 (N); wave tile 64 tiles x 32 couts; block tile 128 x 64; BK = 32 (wino_route.h)
 using route::WBM, route::WBN, route::WBK, route::WNSTAGE;
@@ -1224,48 +1215,21 @@ int winograd_gy_transform(const float* gy, const float* scale, float* Mg, int B,
 
 namespace {
 
-// gradient-producer fusions of a Winograd launch: partial-sum rows = GEMM row tiles of `bm` Winograd tiles each
-struct WinoSums {
-    float *colsum = nullptr, *dot = nullptr, *tmp = nullptr;
-    int begin(WinoParams& p, const gif_conv_epilogue* e, int B, int H, int W, int Co, int bm, const char* who) {
-        if (!e || (!e->colsum && !e->dot)) return 0;
-        GIF_REQUIRE(e->red_ws, "%s: colsum / dot need the red_ws workspace (gif_conv_epilogue_ws_floats)", who);
-        const long per_sample = (long)(H / 2) * (W / 2);
-        GIF_REQUIRE(!e->dot || (e->dot_src && per_sample % bm == 0),
-                    "%s: the dot fusion needs dot_src and a multiple of %d 2x2 tiles per sample (got %ld)", who, bm, per_sample);
-        const long cap = (long)B * H * W / 64 + 16;
-        GIF_REQUIRE(p.tiles_m <= cap, "%s: partial-sum rows exceed the workspace", who);
-        colsum = e->colsum;
-        dot = e->dot;
-        p.part_cs = colsum ? e->red_ws : nullptr;
-        p.part_dot = dot ? e->red_ws + cap * Co : nullptr;
-        tmp = e->red_ws + 2 * cap * Co;
-        return 0;
-    }
-    int finish(const WinoParams& p, int B, int H, int W, int Co, int bm, hipStream_t s) {
-        if (colsum)
-            if (int rc = gif::reduce_partials(p.part_cs, colsum, 1, p.tiles_m, Co, tmp, s)) return rc;
-        if (dot) {
-            // the row padding of the last tile block holds no pixels: ntiles = B * per_sample is a multiple of bm here
-            const int per = (int)((long)(H / 2) * (W / 2) / bm);
-            if (int rc = gif::reduce_partials(p.part_dot, dot, B, per, Co, tmp, s)) return rc;
-        }
-        return 0;
-    }
-};
-
-// everything of WinoParams that comes from the epilogue
-void fill_epilogue(WinoParams& p, const gif_conv_epilogue* e) {
-    p.out_scale = e ? e->out_scale : nullptr;
-    p.bias = e ? e->bias : nullptr;
-    p.residual = e ? static_cast<const float*>(e->residual) : nullptr;
-    p.act = e ? e->act : 0;
-    p.slope = e ? e->slope : 0.f;
-    p.gain = e ? e->gain : 1.f;
-    p.mask_src = e ? static_cast<const float*>(e->mask_src) : nullptr;
-    p.mask_slope = e ? e->mask_slope : 1.f;
-    p.mask_gain = e ? e->mask_gain : 1.f;
-    p.dot_src = e ? static_cast<const float*>(e->dot_src) : nullptr;
+// gradient-producer fusions of a Winograd launch (common.h FusedSums): partial-sum rows = GEMM row tiles of `bm` Winograd tiles each
+int sums_begin(gif::FusedSums& sums, WinoParams& p, const gif_conv_epilogue* e, int B, int H, int W, int Co, int bm, const char* who) {
+    if (int rc = sums.carve(e, (long)B * H * W, Co, who)) return rc;
+    if (!sums.active()) return 0;
+    const long per_sample = (long)(H / 2) * (W / 2);
+    GIF_REQUIRE(!e->dot || (e->dot_src && per_sample % bm == 0),
+                "%s: the dot fusion needs dot_src and a multiple of %d 2x2 tiles per sample (got %ld)", who, bm, per_sample);
+    GIF_REQUIRE(p.tiles_m <= sums.cap, "%s: partial-sum rows exceed the workspace", who);
+    p.part_cs = sums.part_cs;
+    p.part_dot = sums.part_dot;
+    return 0;
+}
+// (the row padding of the last tile block holds no pixels: with a dot fusion ntiles = B * per_sample is a multiple of bm)
+int sums_finish(const gif::FusedSums& sums, const WinoParams& p, int B, int H, int W, int Co, int bm, hipStream_t s) {
+    return sums.reduce(p.tiles_m, Co, B, sums.dot ? (int)((long)(H / 2) * (W / 2) / bm) : 0, s);
 }
 
 // each launches its kernel iff `l` names exactly this instantiation
@@ -1273,27 +1237,21 @@ template <int WN>
 bool mfma_try(const route::WinoLaunch& l, hipStream_t s, const WinoParams& p) {
     if (l.kernel != route::GEMM_MFMA || l.WN != WN) return false;
     static gif::LdsAttr attr;
-    auto kern = wino_gemm_mfma<WN>;
-    attr.ensure(reinterpret_cast<const void*>(kern), l.lds);
-    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), l.lds, s, p);
+    gif::launch_lds(wino_gemm_mfma<WN>, attr, dim3(l.grid), dim3(l.threads), l.lds, s, p);
     return true;
 }
 template <int BM, int BN>
 bool x3_try(const route::WinoLaunch& l, hipStream_t s, const WinoParams& p) {
     if (l.kernel != route::GEMM_X3 || l.BM != BM || l.BN != BN) return false;
     static gif::LdsAttr attr;
-    auto kern = wino_gemm_x3<BM, BN>;
-    attr.ensure(reinterpret_cast<const void*>(kern), l.lds);
-    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), l.lds, s, p);
+    gif::launch_lds(wino_gemm_x3<BM, BN>, attr, dim3(l.grid), dim3(l.threads), l.lds, s, p);
     return true;
 }
 template <int BM, int BN, int NST>
 bool h2_try(const route::WinoLaunch& l, hipStream_t s, const WinoParams& p) {
     if (l.kernel != route::GEMM_H2 || l.BM != BM || l.BN != BN || l.NST != NST) return false;
     static gif::LdsAttr attr;
-    auto kern = wino_gemm_h2<BM, BN, NST>;
-    attr.ensure(reinterpret_cast<const void*>(kern), l.lds);
-    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.threads), l.lds, s, p);
+    gif::launch_lds(wino_gemm_h2<BM, BN, NST>, attr, dim3(l.grid), dim3(l.threads), l.lds, s, p);
     return true;
 }
 
@@ -1332,12 +1290,12 @@ int conv3x3_winograd_impl(int mode, const float* x, const void* U, const void* U
     gif::ProfScope prof(r.family, flops, s, (int)((long)B * H * W), Co, C, split ? 2091 : 1091);
     WinoParams p{};
     p.V = V; p.U = static_cast<const float*>(U); p.y = y;
-    fill_epilogue(p, e);
+    gif::fill_epilogue(p, e);
     p.B = B; p.H = H; p.W = W; p.Co = Co; p.RP = r.RP; p.CP = r.CP;
     p.ntiles = (int)r.ntiles; p.ntiles_pad = (int)r.ntiles_pad; p.TH = H / 2; p.TW = W / 2;
     p.tiles_m = r.primary.tiles_m; p.tiles_n = r.primary.tiles_n;
-    WinoSums sums;
-    if (int rc = sums.begin(p, e, B, H, W, Co, r.sum_tile, entry)) return rc;
+    gif::FusedSums sums;
+    if (int rc = sums_begin(sums, p, e, B, H, W, Co, r.sum_tile, entry)) return rc;
     if (h2) {
         WinoParams q = p;
         q.uexp = static_cast<const int*>(U2);
@@ -1349,7 +1307,7 @@ int conv3x3_winograd_impl(int mode, const float* x, const void* U, const void* U
         }
         if (int rc = wino_launch_one(r.primary, s, q, entry)) return rc;
         if (!q.gate) {  // unguarded
-            if (int rc = sums.finish(p, B, H, W, Co, r.sum_tile, s)) return rc;
+            if (int rc = sums_finish(sums, p, B, H, W, Co, r.sum_tile, s)) return rc;
             return gif::check_launch("conv3x3_winograd_f32h2");
         }
         p.gate = q.gate; p.gate_gen = q.gate_gen; p.h2_stats = gif::h2_stats_words();
@@ -1357,7 +1315,7 @@ int conv3x3_winograd_impl(int mode, const float* x, const void* U, const void* U
     } else {
         if (int rc = wino_launch_one(r.primary, s, p, entry)) return rc;
     }
-    if (int rc = sums.finish(p, B, H, W, Co, r.sum_tile, s)) return rc;
+    if (int rc = sums_finish(sums, p, B, H, W, Co, r.sum_tile, s)) return rc;
     return gif::check_launch(entry);
 }
 

@@ -7,6 +7,8 @@
 // gradient tile, stage depth, twin or profiling family.  NOT modelled here, because they depend on the filled kernel parameters or on
 // run-time state and sit next to the launch: the buffer-addressed form of conv_wgrad_h2v2 (h2v2_buf_ok: GIF_H2_WGRAD_BUF) and
 // GIF_H2_GUARD=0 (no gate: the guarded twin is not launched).
+// What the launches share with the other conv sources (the dynamic-LDS launch helper, the knob reader) is conv_common.h; the weight
+// PACKING entry points are weight_pack.hip's, except the f16x2 ones, which stay in conv_wgrad.hip (see there).
 #pragma once
 #include <stddef.h>
 

@@ -6,6 +6,8 @@
 // input_transform_route / gy_transform_route; the size queries and conv_wgrad.hip (the transforms of the Winograd weight gradient) ask the
 // padding functions.  Nothing else in the library decides a Winograd transform kernel, GEMM tile, ring depth, twin, padded dimension or
 // profiling family of this path.  (The 16 plane GEMMs of the weight gradient are wgrad_route.h's.)
+// The epilogue fields, the fused column-sum / dot workspace (common.h FusedSums) and the dynamic-LDS launch helper are shared with
+// conv_igemm.hip through conv_common.h.
 #pragma once
 #include <stddef.h>
 #include <stdlib.h>
