@@ -232,18 +232,10 @@ __device__ __forceinline__ void split_pair_scalar(const float a0, const float a1
 // and the differencing positions of a Winograd transform produce near-zero groups all the time.  Only a launch in which a row
 // with a group beyond 2^kH2Window meets a FLAGGED weight row (weight gradient: narrow groups on both sides) raises its gate word
 // and is recomputed by the bf16x3 kernel (gated relaunch: the bf16x3 launch that follows returns at once unless the gate is raised).
+// The row exponents and the window statistics are implemented ONCE, in h2_row.h (constants kH2*, H2Row, h2_grow, h2_observe_private,
+// h2_wide, h2_weight_exp / h2_weight_note), with the wave-level forms (h2_group_max, h2_observe, h2_for_rows) in conv_common.h; every
+// f16x2 kernel and both packers call into them.
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-constexpr int kH2Target = 13;        // activations: a new row maximum lands in [2^13, 2^14)
-constexpr int kH2TargetW = 14;       // weights (static): the row maximum lands in [2^14, 2^15)
-constexpr float kH2Limit = 65472.f;  // rescale before |x| * 2^e reaches the f16 overflow threshold (65520)
-constexpr int kH2Window = 14;        // activations: exponent-field distance (row maximum, smallest non-zero group maximum) allowed
-constexpr int kH2WindowW = 16;       // weights: one binade more headroom comes from the tighter scaling target
-// exponent e with m * 2^e in [2^target, 2^(target+1)), clamped to what a float scale factor can hold
-__device__ __host__ __forceinline__ int h2_exp_for(unsigned m_bits, int target) {
-    const int e = target + 127 - (int)((m_bits >> 23) & 0xffu);
-    return e > 126 ? 126 : (e < -126 ? -126 : e);
-}
-__device__ __forceinline__ float h2_pow2(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }  // -126 <= e <= 127
 // one pair of floats -> the packed {x1, x0} f16 dwords of the two terms, 5 VALU and no packed fp32 (v_pk_mul_f32 / v_pk_fma_f32 cost
 // ~32 cycles each beside MFMAs, and with a register-pair element select they returned wrong products while two waves shared a SIMD):
 // 2 v_mul_f32, v_cvt_pk_f16_f32, then v_fma_mixlo_f16 / v_fma_mixhi_f16 — an fp32 FMA with an f16 addend whose result is rounded into

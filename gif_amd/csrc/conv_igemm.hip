@@ -165,7 +165,7 @@ __device__ __forceinline__ void conv_epilogue(const GatherParams& p, f32x16 (&ac
             for (int j = 0; j < NT; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    int row = rbase - c * CR + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    int row = rbase - c * CR + gif::acc_row(r, lh);
                     Cs[row * LDC + wn0 + j * 32 + li] = acc[i][j][r];
                 }
         }
@@ -805,20 +805,8 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
         gif::u32x4_t sa[2][NPL][MT], sb[2][NPL][NT];  // [slot][term][tile]: 8 packed bf16 / f16 each
         f32x4 ra[MT][2], rs[MT][2];                  // raw A fragments (and modulation scales) of the group being split
         const int b3_sw = (li >> 2) & 3;             // (row >> 2) & 3 of every weight row this lane reads
-        // f16x2 row state (lane li and li + 32 hold the same values): exponent, its float 2^e, the largest |a| it can take, the
-        // pending exponent change, and the guard's statistics (row maximum, smallest non-zero group maximum as bits - 1)
-        int h_ex[MT], h_dl[MT];
-        float h_sc[MT], h_lim[MT], h_max[MT];
-        unsigned h_gmin[MT];
+        gif::H2Row hr[MT];    // f16x2 row state (h2_row.h)
         bool h_need = false;  // wave-uniform: some row of this wave changed its exponent in the last `track`
-        if constexpr (H2) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                h_ex[i] = 126; h_dl[i] = 0;
-                h_sc[i] = gif::h2_pow2(126); h_lim[i] = gif::kH2Limit * gif::h2_pow2(-126);
-                h_max[i] = 0.f; h_gmin[i] = 0xFFFFFFFFu;
-            }
-        }
         // LDS reads of group q of stage `buf`: raw fp32 A fragments (split later, piecewise) and the pre-split B operands
         auto read_raw = [&](int buf, int q, int kc, int slot) __attribute__((always_inline)) {
             const T* Ab = As + buf * BM * LD + (wm0 + li) * LD;
@@ -850,39 +838,19 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
                     if (SCALE) { ra[i][0] *= rs[i][0]; ra[i][1] *= rs[i][1]; }
-                    float m = fmaxf(fmaxf(fabsf(ra[i][0][0]), fabsf(ra[i][0][1])), fabsf(ra[i][0][2]));
-                    m = fmaxf(fmaxf(m, fabsf(ra[i][0][3])), fabsf(ra[i][1][0]));
-                    m = fmaxf(fmaxf(m, fabsf(ra[i][1][1])), fabsf(ra[i][1][2]));
-                    m = fmaxf(m, fabsf(ra[i][1][3]));
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                    m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));  // the row's 16 k-values of this group
-                    h_max[i] = fmaxf(h_max[i], m);
-                    h_gmin[i] = min(h_gmin[i], __float_as_uint(m) - 1u);          // an all-zero group (0 - 1 = 0xffffffff) never wins
-                    h_dl[i] = 0;
-                    if (__builtin_amdgcn_ballot_w64(m > h_lim[i]) != 0) {          // wave-uniform (scalar branch), rare after a row's first groups
-                        // per-lane update by selects: no EXEC manipulation anywhere near the MFMA stream
-                        const int ne = m > h_lim[i] ? gif::h2_exp_for(__float_as_uint(m), gif::kH2Target) : h_ex[i];
-                        h_dl[i] = ne - h_ex[i];
-                        h_ex[i] = ne;
-                        h_sc[i] = gif::h2_pow2(ne);
-                        h_lim[i] = ldexpf(gif::kH2Limit, -ne);
-                        h_need = true;
-                    }
+                    gif::h2_observe(hr[i], gif::h2_group_max(ra[i][0], ra[i][1]), h_need);  // the row's 16 k-values of this group
                 }
             }
         };
-        // f16x2: rows whose exponent changed: acc *= 2^(e' - e), exact.  Accumulator register r of a 32x32 tile holds row
-        // (r & 3) + 8 (r >> 2) + 4 lh, whose exponent change lives in lane `row`.
+        // f16x2: rows whose exponent changed: acc *= 2^(e' - e), exact
         auto rescale = [&]() __attribute__((always_inline)) {
             if constexpr (H2) {
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int d = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_dl[i]);
+                    gif::h2_for_rows(lh, hr[i].dl, [&](int r, int d) __attribute__((always_inline)) {
 #pragma unroll
                         for (int j = 0; j < NT; ++j) acc[i][j][r] = ldexpf(acc[i][j][r], d);
-                    }
+                    });
             }
         };
         // piece k of the split of one group: one pair of floats -> one packed dword of each term (bf16x3: 11 VALU, +2 modulated;
@@ -893,7 +861,7 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             float a0 = ra[f][e / 2][(e % 2) * 2], a1 = ra[f][e / 2][(e % 2) * 2 + 1];
             if constexpr (H2) {
                 unsigned h, l;
-                gif::split_pair_h2(a0, a1, h_sc[f], h, l);
+                gif::split_pair_h2(a0, a1, hr[f].sc, h, l);
                 sa[slot][0][f][e] = h; sa[slot][1][f][e] = l;
             } else {
                 if (SCALE) { a0 *= rs[f][e / 2][(e % 2) * 2]; a1 *= rs[f][e / 2][(e % 2) * 2 + 1]; }
@@ -910,8 +878,6 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
         constexpr int NPROD = H2 ? 3 : 6;
         constexpr int LEAD = H2 ? 4 : 6;  // MFMAs ahead of the first piece: they cover the LDS latency of the raw reads
         auto group = [&](int slot, int nslot) __attribute__((always_inline)) {
-            constexpr int TA6[6] = {2, 0, 1, 1, 0, 0}, TB6[6] = {0, 2, 1, 0, 1, 0};
-            constexpr int TA3[3] = {1, 0, 0}, TB3[3] = {0, 1, 0};
             int n = 0, piece = H2 ? -1 : 0;  // piece -1: the tracking step of f16x2
 #pragma unroll
             for (int t = 0; t < NPROD; ++t)
@@ -919,13 +885,14 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
+                        const gif::X3Terms tm = gif::x3_terms<H2>(t);
                         if constexpr (H2)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[slot][TA3[t]][i]),
-                                                                               __builtin_bit_cast(gif::f16x8_t, sb[slot][TB3[t]][j]),
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[slot][tm.a][i]),
+                                                                               __builtin_bit_cast(gif::f16x8_t, sb[slot][tm.b][j]),
                                                                                acc[i][j], 0, 0, 0);
                         else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gif::bf16x8_t, sa[slot][TA6[t]][i]),
-                                                                                __builtin_bit_cast(gif::bf16x8_t, sb[slot][TB6[t]][j]),
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gif::bf16x8_t, sa[slot][tm.a][i]),
+                                                                                __builtin_bit_cast(gif::bf16x8_t, sb[slot][tm.b][j]),
                                                                                 acc[i][j], 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
                         ++n;
@@ -1005,8 +972,7 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             // longer carry 22 bits) ...
             bool wide = false;
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
-                wide |= (int)(__float_as_uint(h_max[i]) >> 23) - (int)((h_gmin[i] + 1u) >> 23) > gif::kH2Window;
+            for (int i = 0; i < MT; ++i) wide |= gif::h2_wide(hr[i]);
             if (p.gate) {
                 // ... AND one of the weight rows it meets was flagged by the packing: a narrow group only costs accuracy where the OTHER
                 // operand is narrow too (common.h: the error floor is 2^(m - 38) of the dot product's largest group product, m = the
@@ -1022,12 +988,10 @@ __device__ __forceinline__ void glds_body(const GatherParams& p, const int bid, 
             for (int j = 0; j < NT; ++j) wex[j] = p.wexp[n0 + wn0 + j * 32 + li];
 #pragma unroll
             for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int er = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_ex[i]);
+                gif::h2_for_rows(lh, hr[i].ex, [&](int r, int er) __attribute__((always_inline)) {
 #pragma unroll
                     for (int j = 0; j < NT; ++j) acc[i][j][r] = ldexpf(acc[i][j][r], -(er + wex[j]));
-                }
+                });
         }
     } else {
     frag_t av[2][MT], bv[2][NT];
@@ -1221,16 +1185,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_rows_thin_h2(const GatherParam
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
-    // running row exponents (glds_body, f16x2): lanes li and li + 32 feed the same row and agree
-    int h_ex[MT], h_dl[MT];
-    float h_sc[MT], h_lim[MT], h_max[MT];
-    unsigned h_gmin[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        h_ex[i] = 126; h_dl[i] = 0;
-        h_sc[i] = gif::h2_pow2(126); h_lim[i] = gif::kH2Limit * gif::h2_pow2(-126);
-        h_max[i] = 0.f; h_gmin[i] = 0xFFFFFFFFu;
-    }
+    gif::H2Row hr[MT];  // running row exponents (h2_row.h)
     // buffer row of this lane's output pixel in row tile i, before the tap shift: pixel index in the tile + 2 halo rows per image row passed
     int a_row[MT];
 #pragma unroll
@@ -1255,49 +1210,28 @@ __global__ void __launch_bounds__(256, 2) conv3x3_rows_thin_h2(const GatherParam
                 gif::u32x4_t sa[2][MT];
                 bool need = false;
 #pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    float m = fmaxf(fmaxf(fabsf(ra[i][0][0]), fabsf(ra[i][0][1])), fabsf(ra[i][0][2]));
-                    m = fmaxf(fmaxf(m, fabsf(ra[i][0][3])), fabsf(ra[i][1][0]));
-                    m = fmaxf(fmaxf(m, fabsf(ra[i][1][1])), fabsf(ra[i][1][2]));
-                    m = fmaxf(m, fabsf(ra[i][1][3]));
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                    m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-                    h_max[i] = fmaxf(h_max[i], m);
-                    h_gmin[i] = min(h_gmin[i], __float_as_uint(m) - 1u);
-                    h_dl[i] = 0;
-                    if (__builtin_amdgcn_ballot_w64(m > h_lim[i]) != 0) {  // wave-uniform, rare after a row's first groups
-                        const int ne = m > h_lim[i] ? gif::h2_exp_for(__float_as_uint(m), gif::kH2Target) : h_ex[i];
-                        h_dl[i] = ne - h_ex[i];
-                        h_ex[i] = ne;
-                        h_sc[i] = gif::h2_pow2(ne);
-                        h_lim[i] = ldexpf(gif::kH2Limit, -ne);
-                        need = true;
-                    }
-                }
+                for (int i = 0; i < MT; ++i) gif::h2_observe(hr[i], gif::h2_group_max(ra[i][0], ra[i][1]), need);
                 if (need) {  // rows whose exponent changed: acc *= 2^(e' - e), exact (every earlier product has been accumulated)
 #pragma unroll
                     for (int i = 0; i < MT; ++i)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int d = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_dl[i]);
-                            acc[i][0][r] = ldexpf(acc[i][0][r], d);
-                        }
+                        gif::h2_for_rows(lh, hr[i].dl, [&](int r, int d) __attribute__((always_inline)) { acc[i][0][r] = ldexpf(acc[i][0][r], d); });
                 }
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         unsigned h, l;
-                        gif::split_pair_h2(ra[i][e / 2][(e % 2) * 2], ra[i][e / 2][(e % 2) * 2 + 1], h_sc[i], h, l);
+                        gif::split_pair_h2(ra[i][e / 2][(e % 2) * 2], ra[i][e / 2][(e % 2) * 2 + 1], hr[i].sc, h, l);
                         sa[0][i][e] = h; sa[1][i][e] = l;
                     }
-                constexpr int TA3[3] = {1, 0, 0}, TB3[3] = {0, 1, 0};  // lo*hi, hi*lo, hi*hi
 #pragma unroll
-                for (int t3 = 0; t3 < 3; ++t3)
+                for (int t3 = 0; t3 < 3; ++t3) {  // lo*hi, hi*lo, hi*hi
+                    const gif::X3Terms tm = gif::x3_terms<true>(t3);
 #pragma unroll
                     for (int i = 0; i < MT; ++i)
-                        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[TA3[t3]][i]),
-                                                                           __builtin_bit_cast(gif::f16x8_t, sb[set][tb][q][TB3[t3]]), acc[i][0], 0, 0, 0);
+                        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[tm.a][i]),
+                                                                           __builtin_bit_cast(gif::f16x8_t, sb[set][tb][q][tm.b]), acc[i][0], 0, 0, 0);
+                }
             }
         }
     };
@@ -1329,7 +1263,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_rows_thin_h2(const GatherParam
     {
         bool wide = false;
 #pragma unroll
-        for (int i = 0; i < MT; ++i) wide |= (int)(__float_as_uint(h_max[i]) >> 23) - (int)((h_gmin[i] + 1u) >> 23) > gif::kH2Window;
+        for (int i = 0; i < MT; ++i) wide |= gif::h2_wide(hr[i]);
         if (p.gate) {
             const bool wflag = p.wexp[p.RP + li] != 0;
             if (__builtin_amdgcn_ballot_w64(wide) != 0 && __builtin_amdgcn_ballot_w64(wflag) != 0 && lane == 0) atomicMax(p.gate, p.gate_gen);
@@ -1337,11 +1271,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_rows_thin_h2(const GatherParam
         const int wex = p.wexp[li];
 #pragma unroll
         for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int er = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_ex[i]);
-                acc[i][0][r] = ldexpf(acc[i][0][r], -(er + wex));
-            }
+            gif::h2_for_rows(lh, hr[i].ex, [&](int r, int er) __attribute__((always_inline)) { acc[i][0][r] = ldexpf(acc[i][0][r], -(er + wex)); });
     }
     conv_epilogue<BM, BN, LD, MT, NT, float, THREADS, false, 2 * AROWS * LD>(p, acc, smem, m0, 0, wm0, 0, tid, li, lh, HWp);
 }

@@ -391,18 +391,19 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
         gif::u32x4_t sa[2][NPL][MT], sb[2][NPL][NT];  // [slot][term][tile]
         float ra[MT][8], rb[NT][8];                   // raw fragments of the group being split
         float psv[MT], qsv[NT];                       // per-sample scales of the stage being split (TAB)
-        // f16x2 state per fragment (channel = lane li of the tile; lanes li and li + 32 agree): exponent, 2^e, the largest |v| it
-        // holds, pending exponent change, the guard's statistics (channel maximum, smallest non-zero group maximum as bits - 1)
+        // f16x2 state per fragment (h2_row.h; its "row" is a channel = lane li of the tile), one array per field of gif::H2Row: f is a
+        // constant only after the group's loops are unrolled, and an array of structs indexed by it costs registers or scratch memory
         int h_ex[NF], h_dl[NF];
         float h_sc[NF], h_lim[NF], h_max[NF];
         unsigned h_gmin[NF];
         bool h_need = false;
         if constexpr (H2) {
+            const gif::H2Row init;
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                h_ex[f] = 126; h_dl[f] = 0;
-                h_sc[f] = gif::h2_pow2(126); h_lim[f] = gif::kH2Limit * gif::h2_pow2(-126);
-                h_max[f] = 0.f; h_gmin[f] = 0xFFFFFFFFu;
+                h_ex[f] = init.ex; h_dl[f] = init.dl;
+                h_sc[f] = init.sc; h_lim[f] = init.lim;
+                h_max[f] = init.max; h_gmin[f] = init.gmin;
             }
         }
         auto scales = [&]() __attribute__((always_inline)) {
@@ -436,38 +437,18 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= sv;
                 }
-                float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
-                m = fmaxf(fmaxf(m, fabsf(v[3])), fabsf(v[4]));
-                m = fmaxf(fmaxf(m, fabsf(v[5])), fabsf(v[6]));
-                m = fmaxf(m, fabsf(v[7]));
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));  // the channel's 16 pixels of this group
-                h_max[f] = fmaxf(h_max[f], m);
-                h_gmin[f] = min(h_gmin[f], __float_as_uint(m) - 1u);
-                h_dl[f] = 0;
-                if (__builtin_amdgcn_ballot_w64(m > h_lim[f]) != 0) {  // wave-uniform (scalar branch), rare after a channel's first groups
-                    // per-lane update by selects: no EXEC manipulation anywhere near the MFMA stream
-                    const int ne = m > h_lim[f] ? gif::h2_exp_for(__float_as_uint(m), gif::kH2Target) : h_ex[f];
-                    h_dl[f] = ne - h_ex[f];
-                    h_ex[f] = ne;
-                    h_sc[f] = gif::h2_pow2(ne);
-                    h_lim[f] = ldexpf(gif::kH2Limit, -ne);
-                    h_need = true;
-                }
+                gif::h2_observe(h_ex[f], h_dl[f], h_sc[f], h_lim[f], h_max[f], h_gmin[f], gif::h2_group_max(v), h_need);  // the channel's 16 pixels of this group
             }
         };
-        // f16x2: acc[i][j][r] *= 2^(change of its P row + change of its Q column); the row (r & 3) + 8 (r >> 2) + 4 lh of P tile i
-        // lives in lane `row`, the column of Q tile j is this lane's own
+        // f16x2: acc[i][j][r] *= 2^(change of its P row + change of its Q column); the column of Q tile j is this lane's own
         auto rescale = [&]() __attribute__((always_inline)) {
             if constexpr (H2) {
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int d = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_dl[i]);
+                    gif::h2_for_rows(lh, h_dl[i], [&](int r, int d) __attribute__((always_inline)) {
 #pragma unroll
                         for (int j = 0; j < NT; ++j) acc[i][j][r] = ldexpf(acc[i][j][r], d + h_dl[MT + j]);
-                    }
+                    });
             }
         };
         constexpr int NPC = NF * 4;
@@ -515,8 +496,6 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
         constexpr int NPROD = H2 ? 3 : 6;
         constexpr int LEAD = H2 ? 3 : 6;  // MFMAs ahead of the first piece: they cover the latency of the 32 ds_read_b32 (issued as 20 ds_read2)
         auto group = [&](int slot, int nslot) __attribute__((always_inline)) {
-            constexpr int TA6[6] = {2, 0, 1, 1, 0, 0}, TB6[6] = {0, 2, 1, 0, 1, 0};
-            constexpr int TA3[3] = {1, 0, 0}, TB3[3] = {0, 1, 0};
             int n = 0, q = 0;
             if constexpr (H2) h_need = false;
 #pragma unroll
@@ -525,13 +504,14 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
+                        const gif::X3Terms tm = gif::x3_terms<H2>(t6);
                         if constexpr (H2)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[slot][TA3[t6]][i]),
-                                                                               __builtin_bit_cast(gif::f16x8_t, sb[slot][TB3[t6]][j]),
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[slot][tm.a][i]),
+                                                                               __builtin_bit_cast(gif::f16x8_t, sb[slot][tm.b][j]),
                                                                                acc[i][j], 0, 0, 0);
                         else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gif::bf16x8_t, sa[slot][TA6[t6]][i]),
-                                                                                __builtin_bit_cast(gif::bf16x8_t, sb[slot][TB6[t6]][j]),
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gif::bf16x8_t, sa[slot][tm.a][i]),
+                                                                                __builtin_bit_cast(gif::bf16x8_t, sb[slot][tm.b][j]),
                                                                                 acc[i][j], 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
                         ++n;
@@ -581,20 +561,17 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
             bool wide_p = false, wide_q = false;  // (a narrow group only costs accuracy where the other operand is narrow too: common.h)
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                const bool wd = (int)(__float_as_uint(h_max[f]) >> 23) - (int)((h_gmin[f] + 1u) >> 23) > gif::kH2Window;
-                if (f < MT) wide_p |= wd;
-                else wide_q |= wd;
+                if (f < MT) wide_p |= gif::h2_wide(h_max[f], h_gmin[f]);
+                else wide_q |= gif::h2_wide(h_max[f], h_gmin[f]);
             }
             if (p.gate && __builtin_amdgcn_ballot_w64(wide_p) != 0 && __builtin_amdgcn_ballot_w64(wide_q) != 0 && lane == 0)
                 atomicMax(p.gate, p.gate_gen);
 #pragma unroll
             for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int er = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_ex[i]);
+                gif::h2_for_rows(lh, h_ex[i], [&](int r, int er) __attribute__((always_inline)) {
 #pragma unroll
                     for (int j = 0; j < NT; ++j) acc[i][j][r] = ldexpf(acc[i][j][r], -(er + h_ex[MT + j]));
-                }
+                });
         }
     } else if (n_begin < n_end) {
         load_global(0);
@@ -618,7 +595,7 @@ __global__ void __launch_bounds__(64 * WAVES_P * WAVES_Q, (X3 == 2 && WAVES_P * 
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            int row = r0 + wp0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            int row = r0 + wp0 + i * 32 + gif::acc_row(r, lh);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 int col = c0 + wq0 + j * 32 + li;
@@ -808,9 +785,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_h2v2(const WgradParams p) {
     // microarchitecture guide's LDS table on 64 banks; this f puts both on distinct 16-byte slots (the direct kernel's (row >> 2) & 3 is
     // conflict free for the reads only: the conversion's stores ran 2-way, 109 M conflict cycles per launch in the round's PMC pass)
     const int wsw = ((tid >> 2) & 1) | ((((tid >> 1) ^ (tid >> 3)) & 1) << 1);
-    int h_ex = 126;
-    float h_sc = gif::h2_pow2(126), h_lim = gif::kH2Limit * gif::h2_pow2(-126), h_max = 0.f;
-    unsigned h_gmin = 0xFFFFFFFFu;
+    gif::H2Row hr;  // (h2_row.h)
     auto convert = [&](int par) __attribute__((always_inline)) {
         float v[32];
 #pragma unroll
@@ -825,26 +800,16 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_h2v2(const WgradParams p) {
         float m0 = 0.f, m1 = 0.f;
 #pragma unroll
         for (int e = 0; e < 16; ++e) { m0 = fmaxf(m0, fabsf(v[e])); m1 = fmaxf(m1, fabsf(v[16 + e])); }
-        const float m = fmaxf(m0, m1);
-        h_max = fmaxf(h_max, m);
-        h_gmin = min(h_gmin, min(__float_as_uint(m0) - 1u, __float_as_uint(m1) - 1u));
-        int d = 0;
-        if (m > h_lim) {  // this channel outgrew its exponent (private state: plain divergence; rare after the first stages)
-            const int ne = gif::h2_exp_for(__float_as_uint(m), gif::kH2Target);
-            d = ne - h_ex;
-            h_ex = ne;
-            h_sc = gif::h2_pow2(ne);
-            h_lim = ldexpf(gif::kH2Limit, -ne);
-            atomicOr(&flags[par], 1);
-        }
-        dexp[tid] = d;
+        // this channel outgrew its exponent (private state: plain divergence; rare after the first stages)
+        if (gif::h2_observe_private(hr, m0, m1)) atomicOr(&flags[par], 1);
+        dexp[tid] = hr.dl;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {  // 8 pixels = one 16-byte chunk of each term
             gif::u32x4_t hi4, lo4;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 unsigned h, l;
-                gif::split_pair_h2(v[8 * j + 2 * k], v[8 * j + 2 * k + 1], h_sc, h, l);
+                gif::split_pair_h2(v[8 * j + 2 * k], v[8 * j + 2 * k + 1], hr.sc, h, l);
                 hi4[k] = h; lo4[k] = l;
             }
             const int phys = (j ^ wsw) << 3;
@@ -863,7 +828,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_h2v2(const WgradParams p) {
             for (int i = 0; i < MT; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int dr = dexp[wp0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh];
+                    const int dr = dexp[wp0 + i * 32 + gif::acc_row(r, lh)];
 #pragma unroll
                     for (int j = 0; j < NT; ++j) acc[i][j][r] = ldexpf(acc[i][j][r], dr + dc[j]);
                 }
@@ -880,15 +845,16 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_h2v2(const WgradParams p) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) sb[tt][j] = *reinterpret_cast<const gif::u32x4_t*>(Op + (tt * 256 + 128 + wq0 + j * 32 + li) * 32 + ch);
             }
-            constexpr int TA3[3] = {1, 0, 0}, TB3[3] = {0, 1, 0};  // lo*hi, hi*lo, hi*hi
 #pragma unroll
-            for (int t3 = 0; t3 < 3; ++t3)
+            for (int t3 = 0; t3 < 3; ++t3) {  // lo*hi, hi*lo, hi*hi
+                const gif::X3Terms tm = gif::x3_terms<true>(t3);
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
                     for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[TA3[t3]][i]),
-                                                                           __builtin_bit_cast(gif::f16x8_t, sb[TB3[t3]][j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gif::f16x8_t, sa[tm.a][i]),
+                                                                           __builtin_bit_cast(gif::f16x8_t, sb[tm.b][j]), acc[i][j], 0, 0, 0);
+            }
         }
     };
 
@@ -907,8 +873,8 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_h2v2(const WgradParams p) {
     }
     // final exponents and the guard (a narrow group only costs accuracy where the other side is narrow too: common.h)
     __syncthreads();
-    fexp[tid] = h_ex;
-    if ((int)(__float_as_uint(h_max) >> 23) - (int)((h_gmin + 1u) >> 23) > gif::kH2Window) atomicOr(&flags[tid < 128 ? 2 : 3], 1);
+    fexp[tid] = hr.ex;
+    if (gif::h2_wide(hr)) atomicOr(&flags[tid < 128 ? 2 : 3], 1);
     __syncthreads();
     if (tid == 0 && p.gate && flags[2] != 0 && flags[3] != 0) atomicMax(p.gate, p.gate_gen);
     int ec[NT];
@@ -930,7 +896,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_h2v2(const WgradParams p) {
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rl = wp0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int rl = wp0 + i * 32 + gif::acc_row(r, lh);
             const int er = fexp[rl];
 #pragma unroll
             for (int j = 0; j < NT; ++j)
@@ -967,10 +933,12 @@ inline void wgrad_launch_v2(bool tab, dim3 grid, hipStream_t s, const WgradParam
 }
 
 // ---- f16x2 weight PACKING (operand of the forward and data-gradient kernels of conv_igemm.hip; the other packings: weight_pack.hip).
-// It is in this translation unit for its device code's sake: gif::h2_exp_for is specialised per translation unit by the targets its callers
-// pass (hipcc internalises device functions and propagates their arguments before inlining).  Here those are kH2TargetW (this kernel)
-// and kH2Target (the f16x2 weight-gradient kernels); with either alone the clamp compiles to other instructions, in this kernel and in
-// nine weight-gradient kernels (conv_wgrad_h2v2: + 2 VGPRs).
+// It is in this translation unit for its device code's sake: gif::h2_exp_for (h2_row.h) takes its target as an ARGUMENT, and hipcc
+// specialises the function per translation unit by the targets its callers pass.  Here those are kH2TargetW (this kernel) and kH2Target
+// (the f16x2 weight-gradient kernels), so the clamp stays a v_min_i32 / s_min_i32.  With the target as a template argument (tried:
+// h2_exp_for<kH2Target>, which would let this kernel move to weight_pack.hip) the clamp became an unsigned compare and a select
+// everywhere: conv_wgrad_h2v2 <0,0,0> 166 -> 168, <0,0,1> 154 -> 156, <1,0,0> 162 -> 164, <1,0,1> 156 -> 158 VGPRs, other opcodes in
+// conv_wgrad_h2v2 <0,1,*>, conv_wgrad_mfma <.., X3 = 2>, the three wino_gemm_h2 and both packing kernels at unchanged registers.
 // f16x2 packing (common.h "h2"): one workgroup per packed row.  Header hdr[r] = the row's exponent e (row maximum over all taps and
 // channels of scale * w lands in [2^14, 2^15)), hdr[RP + r] = the row's flag; planes wp2[t][2][RP][CP] (f16 bits) = hi / lo of
 // scale * w * 2^e.  A 16-channel K group (the kernels' k-groups: 16 consecutive padded channels of one tap) whose maximum lies more
@@ -1013,7 +981,7 @@ __global__ void __launch_bounds__(256) pack_weight_h2_kernel(const float* __rest
         __syncthreads();
     }
     const float rowmax = red[0];
-    const int e2 = gif::h2_exp_for(__float_as_uint(rowmax), gif::kH2TargetW);
+    const int e2 = gif::h2_weight_exp(rowmax);
     const float sc2 = gif::h2_pow2(e2);
     const size_t plane = (size_t)RP * CP;
     const int gpt = CP / 16, ngroups = T * gpt;  // 16-channel groups per tap / per row
@@ -1040,7 +1008,7 @@ __global__ void __launch_bounds__(256) pack_weight_h2_kernel(const float* __rest
                 *reinterpret_cast<unsigned*>(o3 + 2 * plane) = l;
             }
         }
-        if (gm > 0.f && (int)(__float_as_uint(rowmax) >> 23) - (int)(__float_as_uint(gm) >> 23) > gif::kH2WindowW) narrow = true;
+        gif::h2_weight_note(rowmax, gm, narrow);
     }
     if (narrow) atomicOr(&s_flag, 1);
     __syncthreads();
@@ -1382,7 +1350,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_halo_f16(const HaloWgradPar
         for (int t = 0; t < 9; ++t)
             if (t < T9) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) out[(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = acc[t][r];
+                for (int r = 0; r < 16; ++r) out[(t * 32 + gif::acc_row(r, lh)) * 32 + li] = acc[t][r];
             }
     }
 }

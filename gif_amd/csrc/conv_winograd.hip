@@ -532,7 +532,7 @@ __global__ void __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) wino_gemm_mfma(cons
         for (int i = 0; i < MT; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                int row = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                int row = wm0 + i * 32 + gif::acc_row(r, lh);
                 Cs[row * LDC + wn0 + li] = yo[o][i][r];
             }
         __syncthreads();
@@ -754,7 +754,7 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_x3(const WinoParams p) {
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                int row = wm0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                int row = wm0 + gif::acc_row(r, lh);
                 Cs[row * LDC + wn0 + j * 32 + li] = yo[o][j][r];
             }
         __syncthreads();
@@ -851,10 +851,7 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_h2(const WinoParams p) {
     gif::u32x4_t sa[2][2];   // [slot][hi, lo] of the V fragment
     gif::u32x4_t sb[2][NT];  // [hi, lo][cout tile]
     f32x4 ra[2];             // raw V fragments of the group being split
-    // running exponent of this lane's row (lanes li and li + 32 agree) and the guard's statistics (common.h)
-    int h_ex = 126, h_dl = 0;
-    float h_sc = gif::h2_pow2(126), h_lim = gif::kH2Limit * gif::h2_pow2(-126), h_max = 0.f;
-    unsigned h_gmin = 0xFFFFFFFFu;
+    gif::H2Row hr;  // running exponent of this lane's row and the guard's statistics (h2_row.h)
     bool h_need = false;
 
     auto read_a = [&](int buf, int q) __attribute__((always_inline)) {
@@ -868,41 +865,23 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_h2(const WinoParams p) {
         for (int j = 0; j < NT; ++j) sb[t][j] = *reinterpret_cast<const gif::u32x4_t*>(Bb + j * 32 * 32);
     };
     auto track = [&]() __attribute__((always_inline)) {
-        float m = fmaxf(fmaxf(fabsf(ra[0][0]), fabsf(ra[0][1])), fabsf(ra[0][2]));
-        m = fmaxf(fmaxf(m, fabsf(ra[0][3])), fabsf(ra[1][0]));
-        m = fmaxf(fmaxf(m, fabsf(ra[1][1])), fabsf(ra[1][2]));
-        m = fmaxf(m, fabsf(ra[1][3]));
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-        m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        h_max = fmaxf(h_max, m);
-        h_gmin = min(h_gmin, __float_as_uint(m) - 1u);
-        h_dl = 0;
         h_need = false;
-        if (__builtin_amdgcn_ballot_w64(m > h_lim) != 0) {  // wave-uniform, rare
-            const int ne = m > h_lim ? gif::h2_exp_for(__float_as_uint(m), gif::kH2Target) : h_ex;
-            h_dl = ne - h_ex;
-            h_ex = ne;
-            h_sc = gif::h2_pow2(ne);
-            h_lim = ldexpf(gif::kH2Limit, -ne);
-            h_need = true;
-        }
+        gif::h2_observe(hr, gif::h2_group_max(ra[0], ra[1]), h_need);
     };
     // rows whose exponent changed: the position accumulator and the four output accumulators *= 2^(e' - e) (exact)
     auto rescale = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int d = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_dl);
+        gif::h2_for_rows(lh, hr.dl, [&](int r, int d) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 acc[j][r] = ldexpf(acc[j][r], d);
 #pragma unroll
                 for (int o = 0; o < 4; ++o) yo[o][j][r] = ldexpf(yo[o][j][r], d);
             }
-        }
+        });
     };
     auto split_piece = [&](int slot, int e) __attribute__((always_inline)) {
         unsigned h, l;
-        gif::split_pair_h2(ra[e / 2][(e % 2) * 2], ra[e / 2][(e % 2) * 2 + 1], h_sc, h, l);
+        gif::split_pair_h2(ra[e / 2][(e % 2) * 2], ra[e / 2][(e % 2) * 2 + 1], hr.sc, h, l);
         sa[slot][0][e] = h; sa[slot][1][e] = l;
     };
     auto mma = [&](int slot, int ta, int tb) __attribute__((always_inline)) {
@@ -990,7 +969,7 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_h2(const WinoParams p) {
     {
         // (the tracking step after the last stage looked at ring data nobody uses: its statistics may only widen the window check,
         // never narrow it — a spurious fallback at worst; rows >= ntiles are padding and may hold anything: same remark)
-        const bool wide = m0 + wm0 + li < p.ntiles && (int)(__float_as_uint(h_max) >> 23) - (int)((h_gmin + 1u) >> 23) > gif::kH2Window;
+        const bool wide = m0 + wm0 + li < p.ntiles && gif::h2_wide(hr);
         bool wflag = false;
 #pragma unroll
         for (int j = 0; j < NT; ++j) wflag |= p.uexp[p.RP + n0 + wn0 + j * 32 + li] != 0;
@@ -1003,14 +982,12 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_h2(const WinoParams p) {
         int wex[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) wex[j] = p.uexp[n0 + wn0 + j * 32 + li];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int er = __builtin_amdgcn_ds_bpermute(((r & 3) + 8 * (r >> 2) + 4 * lh) * 4, h_ex);
+        gif::h2_for_rows(lh, hr.ex, [&](int r, int er) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < NT; ++j)
 #pragma unroll
                 for (int o = 0; o < 4; ++o) yo[o][j][r] = ldexpf(yo[o][j][r], -(er + wex[j]));
-        }
+        });
     }
 
     // ---- epilogue: for each output position (a,b): transpose through LDS, then coalesced float4 rows
@@ -1043,7 +1020,7 @@ __global__ void __launch_bounds__(512, 1) wino_gemm_h2(const WinoParams p) {
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                int row = wm0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                int row = wm0 + gif::acc_row(r, lh);
                 Cs[row * LDC + wn0 + j * 32 + li] = yo[o][j][r];
             }
         __syncthreads();
@@ -1105,7 +1082,7 @@ __global__ void __launch_bounds__(256) wino_weight_transform_h2(const float* __r
         __syncthreads();
     }
     const float rowmax = red[0];
-    const int e = gif::h2_exp_for(__float_as_uint(rowmax), gif::kH2TargetW);
+    const int e = gif::h2_weight_exp(rowmax);
     const float sc2 = gif::h2_pow2(e);
     const size_t plane = (size_t)RP * CP;
     bool narrow = false;
@@ -1130,7 +1107,7 @@ __global__ void __launch_bounds__(256) wino_weight_transform_h2(const float* __r
             float gm = fabsf(v[q]);  // maximum over the 16 channels of this lane's group
 #pragma unroll
             for (int d = 1; d < 16; d <<= 1) gm = fmaxf(gm, __shfl_xor(gm, d, 16));
-            if (gm > 0.f && (int)(__float_as_uint(rowmax) >> 23) - (int)(__float_as_uint(gm) >> 23) > gif::kH2WindowW) narrow = true;
+            gif::h2_weight_note(rowmax, gm, narrow);
         }
     }
     if (narrow) atomicOr(&s_flag, 1);
