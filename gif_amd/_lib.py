@@ -79,6 +79,9 @@ PROTOTYPES = {
     "gif_flame_skin_bwd_f32": (c_int, [P] * 7 + [c_int] * 4 + [P, P]),
     "gif_flame_joints_f32": (c_int, [P, P, ctypes.POINTER(ctypes.c_int32), P, c_i64, c_int, P, c_i64, c_int, P, c_i64, P, c_i64, P, c_i64,
                                      P, P, c_int, c_int, c_int, P]),
+    "gif_pose_chain_bwd_f32": (c_int, [P, P, ctypes.POINTER(ctypes.c_int32), P, c_i64, c_int, P, c_i64, c_int, P, c_i64, P, c_i64, P, c_i64,
+                                       P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    "gif_landmark_loss_f32": (c_int, [P] * 7 + [c_int, c_int, P]),
     "gif_flame_landmarks_f32": (c_int, [P] * 8 + [c_int] * 7 + [P]),
     "gif_flame_landmarks_bwd_f32": (c_int, [P] * 7 + [c_int] * 5 + [P]),
     "gif_texture_map_f32": (c_int, [P] * 9 + [c_int] * 6 + [P]),

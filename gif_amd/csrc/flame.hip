@@ -5,9 +5,13 @@
 //   vertex  = (sum_j lbs_w[v,j] A_j) . [v_posed, 1]  A_j = the chain's relative transforms, 3x4 row-major
 // Three entry points: gif_flame_joints_f32 (betas, rotations, pose feature and the kinematic chain, one small workgroup per sample),
 // gif_flame_skin_f32 (the two lines above in one launch) and gif_flame_skin_bwd_f32 (their transposes: reductions over V by
-// per-workgroup partial sums and a fixed-order second pass, no float atomics).  All fp32 VALU: 0.18 GFLOP over 11 MB of constants
+// per-workgroup partial sums and a fixed-order second pass, no float atomics); a fourth, gif_pose_chain_bwd_f32, is the backward of the
+// first (its per-sample arithmetic is in flame_chain.h, shared with a host check).  All fp32 VALU: 0.18 GFLOP over 11 MB of constants
 // at B = 32, V = 5023, K = 150 — latency- and bytes-bound, nothing for the matrix cores.
 #include "common.h"
+
+#define GIF_CHAIN_FN __host__ __device__ __forceinline__
+#include "flame_chain.h"
 
 namespace {
 
@@ -296,6 +300,85 @@ __global__ void __launch_bounds__(256) flame_joints_kernel(const JointsParams p)
     if (tid < 12 * p.J) p.A[(long)b * 12 * p.J + tid] = Ao[tid];
 }
 
+// ------------------------------------------------------------------------------------------------------- joints, backward
+struct JointsBwdParams {
+    const float *J0, *Jdirs;       // as the forward
+    const float* src[5];
+    long ld[5];
+    const float *g_A, *g_coef;     // [B][J][12], [B][KP]
+    float* out[5];                 // g_shape, g_expr, g_pose [B][6], g_neck [B][3], g_eye [B][6]: contiguous, null = not computed
+    int parents[kMaxJ];
+    int n_shape, K, KP, J;
+};
+
+// (group, offset) of the axis-angle of joint j, pose_elem's table; joints past the fifth have none
+__device__ __forceinline__ bool pose_slot(int j, int* s, int* o) {
+    if (j == 0) { *s = 2; *o = 0; }
+    else if (j == 1) { *s = 3; *o = 0; }
+    else if (j == 2) { *s = 2; *o = 3; }
+    else if (j < 5) { *s = 4; *o = 3 * (j - 3); }
+    else return false;
+    return true;
+}
+
+// One workgroup per sample, nothing saved by the forward: joints (the forward's 8 interleaved partial sums) and rotations are
+// recomputed, lane 0 walks the chain back (flame_chain.h: J <= 8 dependent 3x3 products), one lane per joint takes Rodrigues'
+// derivative, then lanes over k contract g_jt with Jdirs.  Every sum has one owner and a fixed order: no atomics.
+__global__ void __launch_bounds__(256) flame_joints_bwd_kernel(const JointsBwdParams p) {
+    __shared__ float red[8][32];
+    __shared__ float jt[kMaxJ * 3], r[kMaxJ * 3], R[kMaxJ * 9], GR[kMaxJ * 9], gA[kMaxJ * 12], gF[kMaxJ * 9];
+    __shared__ float gR[kMaxJ * 9], gGt[kMaxJ * 3], gjt[kMaxJ * 3], gr[kMaxJ * 3];
+    __shared__ int par[kMaxJ];
+    const int b = blockIdx.x, tid = threadIdx.x, o = tid & 31, grp = tid >> 5;
+    const int J = p.J, J3 = 3 * J, P = 9 * (J - 1);
+    float sum = 0.f;
+    for (int k = grp; k < p.K; k += 8) {
+        float beta;
+        if (k < p.n_shape) beta = p.src[0] ? p.src[0][b * p.ld[0] + k] : 0.f;
+        else beta = p.src[1] ? p.src[1][b * p.ld[1] + k - p.n_shape] : 0.f;
+        if (o < J3) sum += p.Jdirs[(long)k * J3 + o] * beta;
+    }
+    red[grp][o] = sum;
+    if (tid < J) {
+        int s, off;
+        const bool has = pose_slot(tid, &s, &off);
+        for (int i = 0; i < 3; ++i) r[3 * tid + i] = (has && p.src[s]) ? p.src[s][b * p.ld[s] + off + i] : 0.f;
+        gif::chain_rodrigues(&r[3 * tid], &R[9 * tid]);
+        par[tid] = p.parents[tid];
+    }
+    if (tid < 12 * J) gA[tid] = p.g_A[(long)b * 12 * J + tid];
+    if (tid < P) gF[tid] = p.g_coef[(long)b * p.KP + p.K + tid];
+    __syncthreads();
+    if (tid < J3) {
+        jt[tid] = p.J0[tid] + (((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) +
+                               ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid])));
+    }
+    __syncthreads();
+    if (tid == 0) {
+        gif::chain_world_rotations(J, par, R, GR);
+        gif::chain_reverse(J, par, jt, R, GR, gA, P ? gF : nullptr, gR, gGt, gjt);
+    }
+    __syncthreads();
+    if (tid < J) gif::chain_rodrigues_bwd(&r[3 * tid], &gR[9 * tid], &gr[3 * tid]);
+    for (int k = tid; k < p.K; k += 256) {  // g_betas[k] = g_coef[k] + Jdirs[k] . g_jt, o = 0 .. 3J-1 in order
+        float* dst = k < p.n_shape ? p.out[0] : p.out[1];
+        if (!dst) continue;
+        float acc = p.g_coef[(long)b * p.KP + k];
+        const float* d = p.Jdirs + (long)k * J3;
+        for (int q = 0; q < J3; ++q) acc += d[q] * gjt[q];
+        if (k < p.n_shape) dst[(long)b * p.n_shape + k] = acc;
+        else dst[(long)b * (p.K - p.n_shape) + k - p.n_shape] = acc;
+    }
+    __syncthreads();
+    if (tid < 15) {  // the 15 pose entries, every one written: a joint the model does not have, or has past the fifth, leaves zeros
+        const int j = tid / 3, i = tid - 3 * j;
+        int s, off;
+        pose_slot(j, &s, &off);
+        const int width = s == 3 ? 3 : 6;
+        if (p.out[s]) p.out[s][(long)b * width + off + i] = j < J ? gr[3 * j + i] : 0.f;
+    }
+}
+
 inline bool flame_dims_ok(int B, int V, int KP, int J) {
     return B >= 0 && V >= 0 && KP >= 0 && J >= 1 && J <= kMaxJ && KP >= 9 * (J - 1);
 }
@@ -372,4 +455,28 @@ extern "C" int gif_flame_joints_f32(const float* J0, const float* Jdirs, const i
     p.n_shape = n_shape; p.K = n_shape + n_exp; p.KP = KP; p.J = J;
     flame_joints_kernel<<<B, 256, 0, gif::as_stream(stream)>>>(p);
     return gif::check_launch("flame_joints");
+}
+
+extern "C" int gif_pose_chain_bwd_f32(const float* J0, const float* Jdirs, const int32_t* parents, const float* shape,
+                                      int64_t ld_shape, int n_shape, const float* expr, int64_t ld_expr, int n_exp,
+                                      const float* pose, int64_t ld_pose, const float* neck, int64_t ld_neck, const float* eye,
+                                      int64_t ld_eye, const float* g_A, const float* g_coef, float* g_shape, float* g_expr,
+                                      float* g_pose, float* g_neck, float* g_eye, int B, int KP, int J, gif_stream_t stream) {
+    GIF_REQUIRE(B >= 0 && n_shape >= 0 && n_exp >= 0 && J >= 1 && J <= kMaxJ, "pose_chain_bwd: bad dims (B=%d J=%d; J in 1..8)", B, J);
+    GIF_REQUIRE((long)n_shape + n_exp + 9 * (J - 1) == KP, "pose_chain_bwd: bad dims (KP = %d is not n_shape + n_exp + 9 (J - 1))", KP);
+    if (B == 0 || !(g_shape || g_expr || g_pose || g_neck || g_eye)) return 0;
+    GIF_REQUIRE(parents, "pose_chain_bwd: null pointer (parents)");
+    for (int j = 0; j < J; ++j)
+        GIF_REQUIRE(parents[j] < j && parents[j] >= -1, "pose_chain_bwd: parents[%d] = %d is not an earlier joint", j, parents[j]);
+    GIF_REQUIRE(J0 && g_A && (g_coef || KP == 0) && (Jdirs || n_shape + n_exp == 0), "pose_chain_bwd: null pointer");
+    GIF_REQUIRE((long)B * KP < (1L << 31), "pose_chain_bwd: B * KP must fit 31 bits");
+    JointsBwdParams p{};
+    p.J0 = J0; p.Jdirs = Jdirs; p.g_A = g_A; p.g_coef = g_coef;
+    p.src[0] = shape; p.src[1] = expr; p.src[2] = pose; p.src[3] = neck; p.src[4] = eye;
+    p.ld[0] = ld_shape; p.ld[1] = ld_expr; p.ld[2] = ld_pose; p.ld[3] = ld_neck; p.ld[4] = ld_eye;
+    p.out[0] = n_shape ? g_shape : nullptr; p.out[1] = n_exp ? g_expr : nullptr; p.out[2] = g_pose; p.out[3] = g_neck; p.out[4] = g_eye;
+    for (int j = 0; j < J; ++j) p.parents[j] = parents[j];
+    p.n_shape = n_shape; p.K = n_shape + n_exp; p.KP = KP; p.J = J;
+    flame_joints_bwd_kernel<<<B, 256, 0, gif::as_stream(stream)>>>(p);
+    return gif::check_launch("pose_chain_bwd");
 }

@@ -14,8 +14,8 @@ FlameTextureSpace.forward uses (model/stg2_generator.py:362-364); DESIGN.md §3l
                           `landmark_embedding.npy`); synthetic_landmark_embedding builds one over any face list.
 * FlameLandmarkLayer    — (landmarks2d, landmarks3d) alone: the layer restricted to the few hundred vertices the tables name.
 * project_landmarks     — orthographic projection with y and z flipped, as the reference draws landmarks.
-Kernels: gif_flame_joints_f32, gif_flame_skin_f32, gif_flame_skin_bwd_f32 (csrc/flame.hip), gif_flame_landmarks_f32,
-gif_flame_landmarks_bwd_f32 (csrc/flame_landmarks.hip).  No CPU fallback.
+Kernels: gif_flame_joints_f32, gif_pose_chain_bwd_f32, gif_flame_skin_f32, gif_flame_skin_bwd_f32 (csrc/flame.hip),
+gif_flame_landmarks_f32, gif_flame_landmarks_bwd_f32 (csrc/flame_landmarks.hip).  No CPU fallback.
 """
 import ctypes
 
@@ -299,6 +299,66 @@ class _FlameSkinFn(Function):
         return g_coef, g_A, None, None, None
 
 
+def _group_args(ins):
+    """(address, row stride) per parameter group for the joints kernels, and the tensors that must stay alive until the launch is
+    queued.  A float32 tensor whose columns are adjacent goes in as it is (a column slice of a wider tensor is not copied)."""
+    keep, args = [], []
+    for t in ins:
+        if t is None:
+            args += [None, 0]
+            continue
+        if t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+            t = t.float().contiguous()
+        keep.append(t)
+        args += [t.data_ptr(), t.stride(0)]
+    return args, keep
+
+
+def _launch_pose_chain_bwd(dev, *args):
+    """The one place gif_pose_chain_bwd_f32 is launched from."""
+    _lib.launch("gif_pose_chain_bwd_f32", dev, *args)
+
+
+class _FlameJointsFn(Function):
+    """(coef [B,KP], A [B,J,12]) = gif_flame_joints_f32 of the five parameter groups (None = zeros), the launch of the no-grad path;
+    backward: gif_pose_chain_bwd_f32 on the g_coef / g_A that _FlameSkinFn hands back, one launch for all groups.  Nothing but the
+    inputs themselves is kept: the backward kernel recomputes joints, rotations and the chain."""
+
+    @staticmethod
+    def forward(ctx, consts, dims, shape, exp, pose, neck, eye):
+        J0, Jdirs, parents_c = consts
+        B, n_shape, n_exp, KP, J = dims
+        dev = J0.device
+        ins = [None if t is None else t.detach() for t in (shape, exp, pose, neck, eye)]
+        args, keep = _group_args(ins)
+        coef = torch.empty((B, KP), device=dev, dtype=torch.float32)
+        A = torch.empty((B, J, 12), device=dev, dtype=torch.float32)
+        _lib.launch("gif_flame_joints_f32", dev, J0, Jdirs, parents_c, *args[0:2], n_shape, *args[2:4], n_exp, *args[4:], A, coef,
+                    B, KP, J)
+        ctx.consts, ctx.dims = consts, dims
+        ctx.save_for_backward(*[t for t in ins if t is not None])
+        ctx.present = [t is not None for t in ins]
+        return coef, A
+
+    @staticmethod
+    @once_differentiable  # raw kernel launch: a double backward must fail loudly
+    def backward(ctx, g_coef, g_A):
+        need = ctx.needs_input_grad[2:7]
+        if not any(need):
+            return (None,) * 7
+        J0, Jdirs, parents_c = ctx.consts
+        B, n_shape, n_exp, KP, J = ctx.dims
+        dev = J0.device
+        saved = iter(ctx.saved_tensors)
+        ins = [next(saved) if have else None for have in ctx.present]
+        args, keep = _group_args(ins)
+        outs = [torch.empty((B, n), device=dev, dtype=torch.float32) if want else None
+                for want, n in zip(need, (n_shape, n_exp, 6, 3, 6))]
+        _launch_pose_chain_bwd(dev, J0, Jdirs, parents_c, *args[0:2], n_shape, *args[2:4], n_exp, *args[4:],
+                               g_A.contiguous().float(), g_coef.contiguous().float(), *outs, B, KP, J)
+        return (None, None) + tuple(outs)
+
+
 def _launch_landmarks_bwd(g_lmk, row, tables, g_verts, B, V, R, Ld, Ls):
     """The one place gif_flame_landmarks_bwd_f32 is launched from (on g_verts' device and its current stream)."""
     _lib.launch("gif_flame_landmarks_bwd_f32", g_verts.device, g_lmk, row, *tables, g_verts, B, V, R, Ld, Ls)
@@ -357,10 +417,13 @@ class FlameLayer(nn.Module):
 
     No input requires a gradient: two launches (gif_flame_joints_f32, gif_flame_skin_f32).  Otherwise the joints, the rotations
     and the chain run as torch ops on [B,J,.] tensors — the same J0 + Jdirs . betas form, so both paths compute one function —
-    and autograd carries the skin kernels' g_coef / g_A back through them.  The constants receive no gradient."""
+    and autograd carries the skin kernels' g_coef / g_A back through them.  The constants receive no gradient.
+    `fused_chain=True`: a forward that needs gradients runs the no-grad path's two launches instead (v_posed kept),
+    and the backward of the joints launch is one launch too, gif_pose_chain_bwd_f32, for whichever groups require a gradient."""
 
-    def __init__(self, model, n_shape=100, n_exp=50, landmarks=None, vertex_ids=None):
+    def __init__(self, model, n_shape=100, n_exp=50, landmarks=None, vertex_ids=None, fused_chain=False):
         super().__init__()
+        self.fused_chain = bool(fused_chain)
         if not (0 <= n_shape <= model.n_shape and 0 <= n_exp <= model.n_exp):
             raise ValueError(f"model has {model.n_shape} shape and {model.n_exp} expression columns; asked for {n_shape}, {n_exp}")
         self.n_shape, self.n_exp = n_shape, n_exp
@@ -416,7 +479,7 @@ class FlameLayer(nn.Module):
             (shape_params, self.n_shape, "shape_params"), (expression_params, self.n_exp, "expression_params"),
             (pose_params, 6, "pose_params"), (neck_pose, 3, "neck_pose"), (eye_pose, 6, "eye_pose"))]
         if torch.is_grad_enabled() and any(t.requires_grad for t in given):
-            verts, A = self._forward_grad(B, *ins)
+            verts, A = self._forward_fused(B, ins) if self.fused_chain else self._forward_grad(B, *ins)
         else:
             verts, A = self._forward_nograd(B, ins)
         return (verts,) + self._landmarks(verts, A)
@@ -425,15 +488,7 @@ class FlameLayer(nn.Module):
         dev = self.dirs.device
         V, J = self.lbs_weights.shape
         KP = self.dirs.shape[0]
-        keep, args = [], []
-        for t in ins:  # (address, row stride): views such as flame_batch[:, 0:100] go in as they are, so as addresses
-            if t is None:
-                args += [None, 0]
-                continue
-            if t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
-                t = t.float().contiguous()
-            keep.append(t)  # (alive until both launches are queued)
-            args += [t.data_ptr(), t.stride(0)]
+        args, keep = _group_args(ins)  # views such as flame_batch[:, 0:100] go in as they are; `keep` lives until both launches are queued
         coef = torch.empty((B, KP), device=dev, dtype=torch.float32)
         A = torch.empty((B, J, 12), device=dev, dtype=torch.float32)
         verts = torch.empty((B, V, 3), device=dev, dtype=torch.float32)
@@ -441,6 +496,11 @@ class FlameLayer(nn.Module):
                     self.n_exp, *args[4:], A, coef, B, KP, J)
         _lib.launch("gif_flame_skin_f32", dev, self.v_template, self.dirs, self.lbs_weights, coef, A, verts, None, B, V, KP, J)
         return verts, A
+
+    def _forward_fused(self, B, ins):
+        KP, J = self.dirs.shape[0], self.lbs_weights.shape[1]
+        coef, A = _FlameJointsFn.apply((self.J0, self.Jdirs, self._parents_c), (B, self.n_shape, self.n_exp, KP, J), *ins)
+        return _FlameSkinFn.apply(coef, A, self.v_template, self.dirs, self.lbs_weights), A
 
     def _forward_grad(self, B, shape, exp, pose, neck, eye):
         dev = self.dirs.device
@@ -481,10 +541,10 @@ class FlameLandmarkLayer(FlameLayer):
     the tables remapped to that compact list, so a landmark fit skins those vertices instead of all V, forward and backward.  Same
     arguments as FlameLayer.forward; the landmarks are those of FlameLayer(model, landmarks=embedding)."""
 
-    def __init__(self, model, embedding, n_shape=100, n_exp=50):
+    def __init__(self, model, embedding, n_shape=100, n_exp=50, fused_chain=False):
         embedding.check_vertices(model.lbs_weights.shape[0])
         ids = embedding.vertex_ids()
-        super().__init__(model, n_shape, n_exp, landmarks=embedding.remapped(ids), vertex_ids=ids)
+        super().__init__(model, n_shape, n_exp, landmarks=embedding.remapped(ids), vertex_ids=ids, fused_chain=fused_chain)
 
     def forward(self, shape_params=None, expression_params=None, pose_params=None, neck_pose=None, eye_pose=None):
         return super().forward(shape_params, expression_params, pose_params, neck_pose, eye_pose)[1:]

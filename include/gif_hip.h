@@ -283,6 +283,42 @@ int gif_flame_joints_f32(const float* J0, const float* Jdirs, const int32_t* par
                          const float* neck, int64_t ld_neck, const float* eye, int64_t ld_eye, float* A, float* coef, int B,
                          int KP, int J, gif_stream_t stream);
 
+/* The backward of gif_flame_joints_f32.  Inputs: the forward's (J0, Jdirs, the host array parents, the five
+ * parameter groups as address + row stride, null = zeros), g_A [B][J][12] = dL/d A and g_coef [B][KP] = dL/d coef.  Outputs:
+ * g_shape [B][n_shape], g_expr [B][n_exp], g_pose [B][6], g_neck [B][3], g_eye [B][6], contiguous; each may be null (not
+ * computed), and every element of a given output is written (zeros for a joint the model does not have).  Nothing is saved by
+ * the forward: joints, rotations and the chain are recomputed from the parameters.  With jt = J0 + Jdirs^T betas, R_j =
+ * Rodrigues(r_j), GR_j the world rotations (GR_j = GR_p R_j), g_A_j = [gAR_j | gAt_j] and gF_j the 3x3 block of g_coef behind
+ * the betas (zero for j = 0):
+ *   seeds, every j:        gGR_j = gAR_j - gAt_j jt_j^T,  gGt_j = gAt_j,  gjt_j = -GR_j^T gAt_j
+ *   j = J-1 .. 0, p >= 0:  gR_j = gF_j + GR_p^T gGR_j;  grel = GR_p^T gGt_j;  gjt_j += grel;  gjt_p -= grel;
+ *                          gGR_p += gGR_j R_j^T + gGt_j (jt_j - jt_p)^T;  gGt_p += gGt_j
+ *               a root:    gR_j = gF_j + gGR_j;  gjt_j += gGt_j
+ *   g r_j      = the derivative of Rodrigues' formula as the forward writes it (angle = |r + 1e-8|, dir = r / angle) applied to
+ *                gR_j; r = 0 gives the finite value autograd gives.  It goes to the group joint j reads (global and jaw to
+ *                g_pose, neck, the eyes); joints past the fifth have no parameters.
+ *   g_betas[k] = g_coef[k] + sum_o Jdirs[k][o] gjt[o], split into g_shape and g_expr.
+ * One workgroup per sample, the walk on one lane, the contraction with lanes over k; fixed summation order, no float atomics,
+ * run-to-run identical bits.  B = 0 or every output null: no-op.  J outside 1..8 or KP != n_shape + n_exp + 9 (J - 1): GIF_EINVAL
+ * ("bad dims"); a parents entry that is not an earlier joint or -1, a null operand with work to do: GIF_EINVAL.
+ * (Named for what it differentiates, the pose chain; it lives beside gif_flame_joints_f32 in flame.hip.) */
+int gif_pose_chain_bwd_f32(const float* J0, const float* Jdirs, const int32_t* parents, const float* shape, int64_t ld_shape,
+                           int n_shape, const float* expr, int64_t ld_expr, int n_exp, const float* pose, int64_t ld_pose,
+                           const float* neck, int64_t ld_neck, const float* eye, int64_t ld_eye, const float* g_A,
+                           const float* g_coef, float* g_shape, float* g_expr, float* g_pose, float* g_neck, float* g_eye,
+                           int B, int KP, int J, gif_stream_t stream);
+
+/* The landmark term of a fit: lmk [B][L][3], cam [B][3] = (s, tx, ty), target [B][L][2], weight [B][L] or null (all
+ * ones).  p = (s (x + tx), -s (y + ty)), the first two components of the projection the landmarks are drawn with;
+ *   loss[b] = sum_l weight[b,l] |p[b,l] - target[b,l]|^2          (no normalisation)
+ * and in the same launch g_lmk [B][L][3] = d loss[b] / d lmk[b] (z component written as 0) and g_cam [B][3] = d loss[b] / d
+ * cam[b]; either may be null.  A landmark with weight exactly 0 contributes exactly 0 to the loss and to both gradients, whatever
+ * its target holds (NaN, infinity: a missing detection).  One workgroup per sample, any L, fixed reduction order: run-to-run
+ * identical bits.  B = 0: no-op.  L = 0: loss (and g_cam, when given) is zero-filled.  Negative B or L: GIF_EINVAL ("bad dims");
+ * a null lmk, cam, target or loss with work to do: GIF_EINVAL ("null pointer"). */
+int gif_landmark_loss_f32(const float* lmk, const float* cam, const float* target, const float* weight, float* loss,
+                          float* g_lmk, float* g_cam, int B, int L, gif_stream_t stream);
+
 /* FLAME landmarks: the public definition, smplx lbs.vertices2landmarks / find_dynamic_lmk_idx_and_bcoords as the
  * FLAME layer of photometric_optimization uses them.
  *   landmark[b,l] = sum_{i<3} bary[l,i] verts[b, vid[l,i]],  vid[l] = the three vertex ids of the landmark's embedding face.
