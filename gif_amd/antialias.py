@@ -46,15 +46,17 @@ def _edge_adjacency_host(faces_cpu: np.ndarray) -> np.ndarray:
 
 def edge_adjacency(faces):
     """faces [F,3] or [B,F,3] (the topology of sample 0, shared by the batch) -> edge_adj [F,3] int32 on the faces' device.
-    Built on the host once per topology and cached ON the faces tensor, validated by its in-place version counter (like
-    render._topology)."""
+    Built on the host once per topology and cached ON the faces tensor, validated like render._topology: by the in-place version
+    counter AND the address and geometry of the data (`faces.data = other` keeps the counter).  A write through `.data` into the same
+    storage bumps no counter and moves no address: that one is the caller's to announce, with `del faces._gif_edge_adj`."""
+    key = (faces._version, faces.data_ptr(), tuple(faces.shape), tuple(faces.stride()), str(faces.device))
     cached = getattr(faces, "_gif_edge_adj", None)
-    if cached is None or cached[0] != (faces._version, str(faces.device)):
+    if cached is None or cached[0] != key:
         f2 = faces[0] if faces.ndimension() == 3 else faces
         f_cpu = f2.detach().cpu().numpy().astype(np.int64)
         if f_cpu.size and f_cpu.min() < 0:
             raise _lib.GifHipError("negative face index")
-        cached = ((faces._version, str(faces.device)), torch.from_numpy(_edge_adjacency_host(f_cpu)).to(faces.device))
+        cached = (key, torch.from_numpy(_edge_adjacency_host(f_cpu)).to(faces.device))
         faces._gif_edge_adj = cached
     return cached[1]
 

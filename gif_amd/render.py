@@ -38,10 +38,14 @@ def _topology_csr(faces_cpu: np.ndarray):
 
 def _topology(faces, V, device):
     """(faces [F,3] int32, CSR offsets [V+1], CSR entries [3F]) on `device` for faces [F,3] or [B,F,3] (the topology of
-    sample 0, shared by the batch).  Cached ON the faces tensor (attribute), validated by its in-place version counter: no
-    global cache keyed by an address that could be recycled."""
+    sample 0, shared by the batch).  Cached ON the faces tensor (attribute: no global cache keyed by an address that could be
+    recycled) and validated like the packed weights (ops._cached_weight_op): by the in-place version counter AND the address and
+    geometry of the data — `faces.data = other` keeps the counter, copy.deepcopy copies the attribute to a tensor with a counter of
+    its own.  A write through `.data` into the same storage bumps no counter and moves no address: that one is the caller's to
+    announce, with `del faces._gif_csr`."""
+    key = (faces._version, faces.data_ptr(), tuple(faces.shape), tuple(faces.stride()), V, str(device))
     cached = getattr(faces, "_gif_csr", None)
-    if cached is None or cached[0] != (faces._version, V, str(device)):
+    if cached is None or cached[0] != key:
         f2 = faces[0] if faces.ndimension() == 3 else faces
         f_cpu = f2.detach().cpu().numpy().astype(np.int64)
         if f_cpu.size and (f_cpu.min() < 0 or f_cpu.max() >= V):
@@ -50,7 +54,7 @@ def _topology(faces, V, device):
         off = np.zeros(V + 1, np.int32)
         off[1:len(counts) + 1] = np.cumsum(counts)[:V]
         off[len(counts) + 1:] = off[len(counts)]
-        cached = ((faces._version, V, str(device)),
+        cached = (key,
                   (f2.to(device=device, dtype=torch.int32).contiguous(), torch.from_numpy(off).to(device),
                    torch.from_numpy(ent).to(device)))
         faces._gif_csr = cached
