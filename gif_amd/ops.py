@@ -115,7 +115,8 @@ class GradFuse:
     gif_conv_epilogue ABI 2):
       mask_src (+ slope, gain): the op's output is the gradient w.r.t. a tensor that a fused leaky ReLU produced — multiply by
                                 gain * (mask_src > 0 ? 1 : slope), i.e. FusedLeakyReLU's backward (stylegan2_common_layers.py:22-39);
-      want_colsum             : .colsum [C] = sum over all pixels of the stored output (the bias gradient of that layer);
+      want_colsum             : .colsum [C] = sum over all pixels of the masked output as computed in fp32, before an f16 store rounds or
+                                clamps it (the bias gradient of that layer);
       dot_src                 : .dot [B,C] = sum_hw contraction * dot_src, taken BEFORE out_scale (the modulation gradient of
                                 ModulatedConv2d, :311-320).
     After the launch the results are in .colsum / .dot (fp32)."""

@@ -23,6 +23,36 @@ def host(y, c=None):
     return y.cpu().contiguous()
 
 
+class Flag:
+    """gif_f16_overflow_clear / _watch / _or_into the way train_step.DeviceLossScaler uses them.  The flag pointer reaches a launch
+    only while watching is on (runtime.hip f16_sat_flag): clear() turns it on, or_into() off."""
+
+    def __init__(self):
+        from gif_amd import _lib
+        self.lib = _lib.load()
+        self.stream = torch.cuda.current_stream().cuda_stream
+        self.found = torch.zeros((), device="cuda")
+
+    def clear(self, watch=True):
+        assert self.lib.gif_f16_overflow_clear(self.stream) == 0
+        if not watch:
+            assert self.lib.gif_f16_overflow_watch(0) == 0
+
+    def read(self):
+        self.found.zero_()
+        assert self.lib.gif_f16_overflow_or_into(self.found.data_ptr(), self.stream) == 0
+        return self.found.item()
+
+    def after(self, fn, watch=True):
+        self.clear(watch)
+        out = fn()
+        return self.read(), out
+
+    def restore(self):
+        self.clear()  # leave the word zero and watching off, the state outside a backward pass
+        assert self.lib.gif_f16_overflow_watch(0) == 0
+
+
 def rel_err(got, ref):
     ref = ref.detach().float().cpu()
     got = got.detach().float().cpu()

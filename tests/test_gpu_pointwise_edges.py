@@ -44,6 +44,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_util import Flag as _Flag  # (moved there: tests/test_gpu_f16_flag_sites.py and test_gpu_f16_overflow_chain.py share it)
 from test_gpu_conv_routes import TINY, TOL, _check, fir64
 
 H16 = torch.float16
@@ -309,36 +310,6 @@ def test_pack_nhwc_refusals():
 # failed before this module: the flag tested the fmaxf of the four magnitudes, which drops a NaN beside a finite value, and sat_f16's
 # fminf / fmaxf stored the NaN as -65504 — an f16 gradient NaN reached the loss scaler neither as a flag nor as a value.
 # ---------------------------------------------------------------------------------------------------------------------------------
-class _Flag:
-    """gif_f16_overflow_clear / _watch / _or_into the way train_step.DeviceLossScaler uses them.  The flag pointer reaches a launch
-    only while watching is on (runtime.hip f16_sat_flag): clear() turns it on, or_into() off."""
-
-    def __init__(self):
-        from gif_amd import _lib
-        self.lib = _lib.load()
-        self.stream = torch.cuda.current_stream().cuda_stream
-        self.found = torch.zeros((), device="cuda")
-
-    def clear(self, watch=True):
-        assert self.lib.gif_f16_overflow_clear(self.stream) == 0
-        if not watch:
-            assert self.lib.gif_f16_overflow_watch(0) == 0
-
-    def read(self):
-        self.found.zero_()
-        assert self.lib.gif_f16_overflow_or_into(self.found.data_ptr(), self.stream) == 0
-        return self.found.item()
-
-    def after(self, fn, watch=True):
-        self.clear(watch)
-        out = fn()
-        return self.read(), out
-
-    def restore(self):
-        self.clear()  # leave the word zero and watching off, the state outside a backward pass
-        assert self.lib.gif_f16_overflow_watch(0) == 0
-
-
 FLAG_VALUES = [("next", float(torch.tensor(65504.0).nextafter(torch.tensor(math.inf)))), ("pinf", math.inf), ("ninf", -math.inf),
                ("nan", math.nan)]
 
