@@ -7,7 +7,8 @@
 // parameters (and EMA parameters) stay wherever torch allocated them and are reached through a chunk table, so model.to(),
 // load_state_dict() or checkpoint code never see a re-bound storage.
 // Arithmetic follows torch's single-tensor Adam: m = lerp(m, g, 1 - b1); v = v * b2 + (1 - b2) * g * g;
-// p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps), step_size = lr / bc1 (bias corrections computed on the host in double).
+// p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps), step_size = lr / bc1 (bias corrections computed on the host in double;
+// with a device-side count, per workgroup in double from the count of the chunk's own parameter).
 #include "common.h"
 
 namespace {
@@ -37,13 +38,14 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
 
 __global__ void __launch_bounds__(256) adam_ema_kernel(AdamArgs a) {
     if (a.found_inf && *a.found_inf != 0.f) return;  // uniform over the grid: nobody updates (GradScaler semantics)
-    if (a.dev_step) {  // loss-scaled run: skipped steps do not advance the count, so the corrections come from the device
-        const double t = (double)*a.dev_step;
+    const gif_adam_chunk c = a.chunks[blockIdx.x];
+    if (a.dev_step) {  // the count lives on the device: a loss-scaled run (skipped steps do not advance it) or unequal counts
+        // this chunk's parameter has taken step_offset fewer steps than the count says (it joined later): its own count corrects it
+        const double t = (double)*a.dev_step - (double)c.step_offset;
         a.step_size = (float)((double)a.lr / (1.0 - pow((double)a.b1, t)));
         a.bc2_sqrt = (float)sqrt(1.0 - pow((double)a.b2, t));
     }
     const float gs = a.inv_scale ? *a.inv_scale : 1.f;
-    const gif_adam_chunk c = a.chunks[blockIdx.x];
     float* __restrict__ p = c.param;
     float* __restrict__ e = c.ema;
     const float* __restrict__ g = a.g + c.flat_offset;

@@ -4,6 +4,12 @@ optionally fused with the EMA update of the running generator (generic_utils.acc
 Drop-in for the optimisers of train.py:364-381 in the one-process-per-GPU loop: same constructor hyper-parameters, same
 update arithmetic (torch's single-tensor Adam, no weight decay / amsgrad), and a state_dict() in torch.optim.Adam's format
 (`exp_avg`, `exp_avg_sq`, `step` per parameter) so checkpoints written by either load into the other (train.py:254-265).
+state_dict() is a snapshot: every entry is a tensor of its own (a `step` per parameter, copies of the moments), so an optimiser
+that loads it shares nothing with this one.  Like torch, FlatAdam counts steps PER PARAMETER: load_state_dict() keeps each
+parameter's saved count, a bucket parameter without saved state (a generator block that joins at a resolution switch,
+train.py:93) starts at 0 with zero moments, and step() corrects each parameter's bias by its own count.  Internally that is one
+count (host scalar, or device scalar under loss scaling) plus a constant lag per parameter in the chunk table; while every
+lag is 0 — any run that did not load unequal counts — the launch is the one it always was.
 Parameters keep their own storage; gradients / exp_avg / exp_avg_sq are views into flat buffers that share the bucket's
 offset table.  Parameters outside the bucket (no gradient at the current resolution) are skipped exactly like torch's Adam
 skips parameters whose .grad is None.  There is no CPU path: the kernel needs device tensors.
@@ -17,7 +23,7 @@ from . import _lib
 
 class _Chunk(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("ema", ctypes.c_void_p), ("flat_offset", ctypes.c_int64),
-                ("n", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("n", ctypes.c_int32), ("step_offset", ctypes.c_int32)]
 
 
 class FlatAdam(torch.optim.Adam):
@@ -32,10 +38,16 @@ class FlatAdam(torch.optim.Adam):
             raise _lib.GifHipError("FlatAdam runs on the HIP device only (no CPU fallback); use torch.optim.Adam on CPU")
         self._m = torch.zeros_like(bucket.flat)
         self._v = torch.zeros_like(bucket.flat)
-        self._step_t = torch.tensor(0.0)  # shared by every parameter's state (torch keeps one CPU scalar per parameter)
+        # the count of the parameters that have been here longest; shared by every parameter's state INSIDE the optimiser
+        # (torch keeps one CPU scalar per parameter; state_dict() hands out such scalars, each count less its parameter's lag)
+        self._step_t = torch.tensor(0.0)
+        self._lag = [0] * len(bucket.params)  # per bucket parameter: steps it has taken fewer than _step_t says
+        self._uneven = False  # any lag non-zero
         # loss-scaled runs (found_inf given): the step count lives on the device and only advances on steps that were applied,
-        # like torch's GradScaler-aware Adam; _step_t is refreshed from it when a state_dict is taken
+        # like torch's GradScaler-aware Adam; _step_t is refreshed from it when a state_dict is taken.  Unequal counts keep it too:
+        # the kernel forms per-parameter corrections from a device count only
         self._step_dev = None
+        self._host_stale = False  # loss-scaled steps since _step_t was last read back from _step_dev
         index = {id(p): i for i, p in enumerate(params)}
         self._ema = None
         if ema_params is not None:
@@ -55,7 +67,7 @@ class FlatAdam(torch.optim.Adam):
 
     # ---- chunk table ---------------------------------------------------------------------------------------------
     def _chunks(self):
-        key = tuple(p.data_ptr() for p in self.bucket.params)
+        key = tuple(p.data_ptr() for p in self.bucket.params) + tuple(self._lag)
         if self._ema is not None:
             key += tuple(e.data_ptr() for e in self._ema)
         if key == self._table_key:
@@ -71,7 +83,8 @@ class FlatAdam(torch.optim.Adam):
                 raise _lib.GifHipError("FlatAdam: EMA parameter does not mirror its parameter")
             n = p.numel()
             for s in range(0, n, cf):
-                rows.append((p.data_ptr() + 4 * s, (e.data_ptr() + 4 * s) if e is not None else 0, off + s, min(cf, n - s), 0))
+                rows.append((p.data_ptr() + 4 * s, (e.data_ptr() + 4 * s) if e is not None else 0, off + s, min(cf, n - s),
+                             self._lag[k]))
         arr = (_Chunk * len(rows))(*rows)
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8) if rows else torch.empty(0, dtype=torch.uint8)
         self._table = (host.to(self.bucket.flat.device), len(rows))
@@ -100,14 +113,20 @@ class FlatAdam(torch.optim.Adam):
             if self._step_dev is None:
                 self._step_dev = torch.full((), float(self._step_t.item()), device=self.bucket.flat.device)
             self._step_dev.add_(1.0 - found_inf.clamp(0.0, 1.0))  # a skipped step does not advance the bias corrections
+            self._host_stale = True
             dev_step = self._step_dev
             t = 1  # (host-side corrections unused: the kernel derives them from the device counter)
         else:
-            if self._step_dev is not None:  # leaving a loss-scaled phase: continue from the device count
-                self._step_t.fill_(float(self._step_dev.item()))
-                self._step_dev = None
+            self._read_back_count()  # leaving a loss-scaled phase: continue from the device count
             self._step_t += 1
             t = int(self._step_t.item())
+            if not self._uneven:
+                self._step_dev = None
+            elif self._step_dev is None:  # unequal counts: the kernel needs the count itself, not two corrections
+                self._step_dev = torch.full((), float(t), device=self.bucket.flat.device)
+            else:
+                self._step_dev.add_(1.0)
+            dev_step = self._step_dev
         table, n = self._chunks()
         has_ema = self._ema is not None and ema_decay is not None
         lib = _lib.load()
@@ -138,16 +157,33 @@ class FlatAdam(torch.optim.Adam):
         previous step's values in the bucket for any parameter the next backward does not reach)."""
         self.bucket.zero()
 
-    def state_dict(self):
-        if self._step_dev is not None:
+    def _read_back_count(self):
+        if self._host_stale:
             self._step_t.fill_(float(self._step_dev.item()))
-        return super().state_dict()
+            self._host_stale = False
+
+    def state_dict(self):
+        """torch.optim.Adam's format.  Every tensor is a copy: `step` is a CPU scalar per parameter holding that parameter's own
+        count (never the shared internal one: torch's Adam would add 1 to it once per parameter), the moments leave the flat
+        buffers (an optimiser that loads the dict directly keeps the tensors it is given)."""
+        self._read_back_count()
+        sd = super().state_dict()
+        count = float(self._step_t)
+        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        state = dict(sd["state"])
+        for p, lag in zip(self.bucket.params, self._lag):
+            st = self.state[p]
+            state[index[id(p)]] = {"step": torch.tensor(count - lag, dtype=torch.float32), "exp_avg": st["exp_avg"].clone(),
+                                   "exp_avg_sq": st["exp_avg_sq"].clone()}
+        sd["state"] = state
+        return sd
 
     # ---- checkpoint compatibility --------------------------------------------------------------------------------
     def load_state_dict(self, state_dict):
-        """Accepts torch.optim.Adam / FlatAdam state dicts: the loaded moments are copied into the flat buffers."""
+        """Accepts torch.optim.Adam / FlatAdam state dicts: the loaded moments are copied into the flat buffers and every
+        parameter keeps its saved count; a bucket parameter without saved state starts at count 0 with zero moments."""
         super().load_state_dict(state_dict)
-        step = 0.0
+        counts = []
         for p, off in zip(self.bucket.params, self.bucket.offsets):
             st = self.state.get(p)
             n = p.numel()
@@ -155,10 +191,16 @@ class FlatAdam(torch.optim.Adam):
             if st:
                 m.copy_(st["exp_avg"])
                 v.copy_(st["exp_avg_sq"])
-                step = max(step, float(st["step"]))
+                counts.append(int(round(float(st["step"]))))
             else:
                 m.zero_()
                 v.zero_()
+                counts.append(0)
             self.state[p] = {"step": self._step_t, "exp_avg": m, "exp_avg_sq": v}
-        self._step_t.fill_(step)
-        self._step_dev = None  # a device-side count from before the load is stale: the next loss-scaled step re-seeds it from _step_t
+        step = max(counts, default=0)
+        self._lag = [step - c for c in counts]
+        self._uneven = any(self._lag)
+        self._step_t.fill_(float(step))
+        # a device-side count from before the load is stale: the next step that needs one re-seeds it from _step_t
+        self._step_dev = None
+        self._host_stale = False

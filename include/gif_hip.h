@@ -775,16 +775,21 @@ int gif_linear_bank_bwd_f32(const float* x, int M, int K, int ldx, const gif_lin
  * `ema` may be NULL per chunk) are addressed through a DEVICE array of chunks, each at most gif_adam_chunk_floats() elements.
  *   m += (g - m)*(1 - beta1);  v = v*beta2 + (1 - beta2)*g*g;  p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
  *   ema = ema*ema_decay + (1 - ema_decay)*p      (has_ema != 0)
- * bias_correction1/2 = 1 - beta^step are computed by the caller (host, double).
+ * bias_correction1/2 = 1 - beta^step are computed by the caller (host, double) and hold for every chunk when dev_step is NULL.
  * Loss scaling (f16 activation path): inv_grad_scale / found_inf are optional DEVICE scalars — every gradient is multiplied
  * by *inv_grad_scale, and when *found_inf != 0 the launch changes nothing (an overflowed step is skipped without a host sync).
+ * dev_step: optional DEVICE scalar, the step count including this step.  When given, bias_correction1/2 are ignored and each
+ * workgroup forms its corrections in double from the fp32 betas and the count of ITS parameter, *dev_step - step_offset: like
+ * torch.optim.Adam, a parameter that joined the optimiser later (progressive growing, a checkpoint with unequal counts) is
+ * corrected by the steps it has taken itself.  The caller keeps *dev_step - step_offset >= 1 on every applied step.
+ * Without dev_step the kernel knows no count and step_offset must be 0 in every chunk (it is not read).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct gif_adam_chunk {
     float* param;        /* first element of this chunk in the parameter tensor */
     float* ema;          /* same element of the EMA copy, or NULL */
     int64_t flat_offset; /* offset of the chunk in the flat grad / exp_avg / exp_avg_sq buffers */
     int32_t n;           /* elements in this chunk (<= gif_adam_chunk_floats()) */
-    int32_t reserved;
+    int32_t step_offset; /* steps this parameter lags behind *dev_step (>= 0; 0: the count is its own).  Was `reserved`, 0. */
 } gif_adam_chunk;
 int gif_adam_chunk_floats(void);
 int gif_adam_ema_step_f32(const gif_adam_chunk* chunks, int nchunks, const float* grad_flat, float* exp_avg_flat,

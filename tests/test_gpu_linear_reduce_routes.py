@@ -37,6 +37,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import adam_ref
+
 pytestmark = pytest.mark.gpu
 
 H16 = torch.float16
@@ -45,7 +47,7 @@ NAN = float("nan")
 U32 = 2.0 ** -24  # unit round-off of fp32
 
 # per-element tolerances (see the module docstring for the measurements behind them)
-TOL = {"gemm": 1e-6, "style": 1.2e-6, "bank": 1.2e-6, "sum32": 1.2e-6, "sum16": 1e-6, "ew16": 7e-4, "sample": 5e-7, "adam": 1e-6,
+TOL = {"gemm": 1e-6, "style": 1.2e-6, "bank": 1.2e-6, "sum32": 1.2e-6, "sum16": 1e-6, "ew16": 7e-4, "sample": 5e-7, "adam": adam_ref.TOL_ADAM,
        "route": 4e-6}
 TINY = 1e-30
 WORST = {}  # family -> (worst ratio so far, case)
@@ -773,21 +775,7 @@ ADAM_ROWS = [
 ]
 
 
-def _f32(v):
-    return float(np.float32(v))
-
-
-def _adam_ref(p, g, m, v, t, lr, b1, b2, eps, device_step):
-    """torch's single-tensor Adam in fp64 over the kernel's operands: lr, betas and eps arrive as fp32; the bias corrections are
-    formed in double from the Python betas (host) or from the fp32 betas (device step count of a loss-scaled step)."""
-    lrf, b1f, b2f, epsf = _f32(lr), _f32(b1), _f32(b2), _f32(eps)
-    m2 = b1f * m + (1 - b1f) * g
-    v2 = b2f * v + (1 - b2f) * g * g
-    c1, c2 = (b1f, b2f) if device_step else (b1, b2)
-    bc1, bc2 = 1 - c1 ** t, 1 - c2 ** t
-    denom = v2.sqrt() / math.sqrt(bc2) + epsf
-    upd = lrf / bc1 * m2 / denom
-    return p - upd, m2, v2, upd
+_f32, _adam_ref = adam_ref.f32, adam_ref.adam_ref  # (shared with test_gpu_resume)
 
 
 @pytest.mark.parametrize("row", ADAM_ROWS, ids=[r[0] for r in ADAM_ROWS])
@@ -835,9 +823,10 @@ def test_flat_adam(row):
             gd = gr.double() * (0.25 if scaled else 1.0)
             pr, mr, vr, upd = _adam_ref(p0, gd, m0, v0, t, lr, b1, b2, eps, scaled)
             what = f"{name} step{step} p{i} n{sizes[i]}"
-            _check(opt.state[p]["exp_avg"], mr, m0.abs() + gd.abs(), "adam", f"{what} m")
-            _check(opt.state[p]["exp_avg_sq"], vr, vr.abs(), "adam", f"{what} v")
-            _check(p, pr, p0.abs() + 4 * upd.abs(), "adam", f"{what} p")
+            Rm, Rv, Rp = adam_ref.adam_bounds(p0, gd, m0, vr, upd)  # |m0| + |g|, |v|, |p0| + 4 |upd|
+            _check(opt.state[p]["exp_avg"], mr, Rm, "adam", f"{what} m")
+            _check(opt.state[p]["exp_avg_sq"], vr, Rv, "adam", f"{what} v")
+            _check(p, pr, Rp, "adam", f"{what} p")
             if ema_on:
                 df = _f32(decay)
                 er = e0 * df + (1 - df) * p.detach().cpu().double()  # (the kernel blends its own new p)
