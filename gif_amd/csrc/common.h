@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "ew_route.h"
 #include "gif_hip.h"
 
 namespace gif {
@@ -37,6 +38,11 @@ inline hipStream_t as_stream(gif_stream_t s) { return reinterpret_cast<hipStream
 inline const char* knob(const char* name) {
     static const bool on = [] { const char* e = ::getenv("GIF_EXPERIMENTAL"); return e && atoi(e) != 0; }();
     return on ? ::getenv(name) : nullptr;
+}
+// integer value of such a knob, `unset` when it is not given (or not honoured)
+inline int knob_int(const char* name, int unset) {
+    const char* e = knob(name);
+    return e ? atoi(e) : unset;
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
@@ -94,14 +100,12 @@ struct ProfScope {
     ~ProfScope();
 };
 
-// ---- fixed-order reduction of per-tile partial sums (elementwise.hip): out[y][c] = sum_k partial[y][k][c], y < Y, k < nblk.
-// Long single-group reductions (Y == 1, nblk > 512) go through `tmp` (>= 64 * C floats) in two launches.
-int reduce_partials(const float* partial, float* out, int Y, int nblk, int C, float* tmp, hipStream_t s);
-// The red_ws workspace of an epilogue reduction over `rows` output rows.  epilogue_ws_rows and FusedSums describe the SAME buffer: `cap`
-// partial rows of column sums, `cap` of dot products (conv tiles of >= 64 rows), then tmp (FIR blocks <= 4096 rows + the 64 of
-// reduce_partials) — the first is what callers allocate (in rows of Co floats), the second how a convolution launch carves it up.
-inline int64_t epilogue_ws_cap(int64_t rows) { return rows / 64 + 16; }
-inline int64_t epilogue_ws_rows(int64_t rows) { return 2 * epilogue_ws_cap(rows) + 4096 + 64; }
+// ---- fixed-order reduction of per-tile partial sums (elementwise.hip): out[y][c] = sum_k partial[y][k][c], y < Y, k < nblk, in the
+// stages of ew_route.h reduce_plan.  The staged plans write up to plan.tmp_rows rows of C floats to `tmp`, which holds `tmp_rows` rows
+// (sized by ew_route.h reduce_tmp_rows / reduce_tmp_rows_single / epilogue_tmp_rows); a plan that needs more fails with GIF_EINVAL.
+int reduce_partials(const float* partial, float* out, int Y, int nblk, int C, float* tmp, long tmp_rows, hipStream_t s);
+// The red_ws workspace of an epilogue reduction: ew_route.h epilogue_ws_rows is what callers allocate (in rows of Co floats), FusedSums
+// how a convolution launch carves the SAME buffer up.
 // Gradient-producer fusions of one convolution (direct or Winograd): carve the partial-sum buffers out of red_ws before the launches,
 // reduce them in a fixed order after.  The caller checks its own preconditions (what its tiles must divide) between the two.
 struct FusedSums {
@@ -117,7 +121,7 @@ struct FusedSums {
         GIF_REQUIRE(e->red_ws, "%s: colsum / dot need the red_ws workspace (gif_conv_epilogue_ws_floats)", who);
         colsum = e->colsum;
         dot = e->dot;
-        cap = (long)epilogue_ws_cap(rows);
+        cap = gif_ew::epilogue_ws_cap(rows);
         part_cs = colsum ? e->red_ws : nullptr;
         part_dot = dot ? e->red_ws + cap * Co : nullptr;
         tmp = e->red_ws + 2 * cap * Co;
@@ -126,9 +130,9 @@ struct FusedSums {
     // column sums over the `rows` partial rows the launches wrote, then the dot products of the B samples (rows_per_sample rows each)
     int reduce(int rows, int Co, int B, int rows_per_sample, hipStream_t s) const {
         if (colsum)
-            if (int rc = reduce_partials(part_cs, colsum, 1, rows, Co, tmp, s)) return rc;
+            if (int rc = reduce_partials(part_cs, colsum, 1, rows, Co, tmp, gif_ew::epilogue_tmp_rows(), s)) return rc;
         if (dot)
-            if (int rc = reduce_partials(part_dot, dot, B, rows_per_sample, Co, tmp, s)) return rc;
+            if (int rc = reduce_partials(part_dot, dot, B, rows_per_sample, Co, tmp, gif_ew::epilogue_tmp_rows(), s)) return rc;
         return 0;
     }
 };

@@ -35,12 +35,6 @@ __device__ __host__ __forceinline__ constexpr X3Terms x3_terms(int t) {
     }
 }
 
-// integer value of a GIF_* knob (common.h knob: honoured under GIF_EXPERIMENTAL=1 only), `unset` when it is not given
-inline int knob_int(const char* name, int unset) {
-    const char* e = knob(name);
-    return e ? atoi(e) : unset;
-}
-
 // "This kernel may use `lds` bytes of dynamic LDS on the current device", then the launch.  `attr` belongs to ONE kernel instantiation
 // (LdsAttr::granted is per kernel): every call site keeps a static of its own per instantiation.
 template <typename K, typename P>

@@ -913,7 +913,7 @@ void wgrad_launch(dim3 grid, int threads, hipStream_t s, const WgradParams& p) {
 
 // buffer-addressed DMA of conv_wgrad_h2v2: both operands (per plane in planes mode) within 3.5 GiB; GIF_H2_WGRAD_BUF=0: the 64-bit form (A/B)
 inline bool h2v2_buf_ok(const WgradParams& p) {
-    static const int off = gif::knob("GIF_H2_WGRAD_BUF") ? atoi(gif::knob("GIF_H2_WGRAD_BUF")) == 0 : 0;
+    static const int off = gif::knob_int("GIF_H2_WGRAD_BUF", 1) == 0;
     // byte offsets are unsigned 32-bit; rows a stage reaches past the end of a tensor (the last split's tail, < 32 pixels) must stay out of
     // range without wrapping: 512 MiB of headroom below 4 GiB (the 64-sample discriminator pass on the blurred 257^2 map is 2.16 GB)
     const long lim = (1L << 32) - (1L << 29);

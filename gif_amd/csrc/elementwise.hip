@@ -524,14 +524,6 @@ __global__ void __launch_bounds__(256) colsum_stage2(const float* __restrict__ p
     if (rl == 0 && c < C) out[(size_t)blockIdx.y * C + c] = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
 }
 
-inline int colsum_blocks(long nrows, int C4) {
-    int R = 256 / C4;
-    long want = (nrows + (long)R * 16 - 1) / ((long)R * 16);  // >= 16 rows per row-lane
-    if (want > 512) want = 512;
-    if (want < 1) want = 1;
-    return (int)want;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // minibatch stddev (stg2_discriminator.py:59-65)
 // ---------------------------------------------------------------------------------------------------------
@@ -698,11 +690,9 @@ __global__ void __launch_bounds__(256) bilinear_down_bwd_kernel(const float* __r
     }
 }
 
-inline int ew_grid(long n) {
-    long b = (n + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (int)b;
+const gif_ew::FirKnobs& fir_knobs() {
+    static const gif_ew::FirKnobs once = gif_ew::parse_fir_knobs(gif::knob("GIF_FIR_BLOCK"));
+    return once;
 }
 
 template <typename T>
@@ -723,57 +713,47 @@ int upfirdn2d_impl(const T* x, const float* k, T* y, int B, int Hi, int Wi, int 
     p.padx0 = padx0; p.pady0 = pady0; p.KH = KH; p.KW = KW; p.flip = flip;
     p.sat_flag = sizeof(T) == 2 ? gif::f16_sat_flag() : nullptr;
     // gradient-producer fusions (blur kernels): leaky-ReLU-backward mask + bias-gradient column sums in the epilogue
-    const bool blur = up == 1 && down == 1 && KH == 4 && KW == 4;
-    const bool fused = e && (e->mask_src || e->colsum || e->dot || e->dot_src);
     float* colsum_out = nullptr;
-    if (fused) {
+    if (e && (e->mask_src || e->colsum || e->dot || e->dot_src)) {
         GIF_REQUIRE(!e->dot && !e->dot_src, "upfirdn2d: the dot fusion is a convolution epilogue only");
-        GIF_REQUIRE(blur, "upfirdn2d: mask / colsum fusions need the 4x4 blur form (up = down = 1)");
+        GIF_REQUIRE(up == 1 && down == 1 && KH == 4 && KW == 4, "upfirdn2d: mask / colsum fusions need the 4x4 blur form (up = down = 1)");
         GIF_REQUIRE(!e->colsum || (e->red_ws && (C & (C - 1)) == 0 && C <= 1024), "upfirdn2d: colsum needs red_ws and a power-of-two C <= 1024");
         p.mask_src = static_cast<const T*>(e->mask_src);
         p.mask_slope = e->mask_slope; p.mask_gain = e->mask_gain;
         colsum_out = e->colsum;
         p.part_cs = colsum_out ? e->red_ws : nullptr;
     }
+    const gif_ew::FirRoute r = gif_ew::fir_route({B, C, Ho, Wo, up, down, padx0, pady0, KH, KW}, colsum_out != nullptr, fir_knobs());
+    const dim3 grid(r.grid_x, r.grid_y);
     hipStream_t s = gif::as_stream(stream);
-    if (blur && (long)B * ((Ho + 15) / 16) * ((Wo + 3) / 4) * (C / 4) >= 256L * 256 * 2) {
-        // enough columns strips to fill the chip with 16-row sliding windows
-        long total = (long)B * ((Ho + 15) / 16) * ((Wo + 3) / 4) * (C / 4);
-        const int grid = ew_grid(total);
-        blur4x4_rows_kernel<T, 16, 4><<<grid, 256, 0, s>>>(p);
-        if (colsum_out) return gif::reduce_partials(p.part_cs, colsum_out, 1, grid, C, p.part_cs + (size_t)grid * C, s);
-        return gif::check_launch("upfirdn2d(blur rows)");
+    const char* what = "upfirdn2d";
+    switch (r.kernel) {
+    case gif_ew::FIR_BLUR_ROWS:
+        blur4x4_rows_kernel<T, 16, 4><<<grid, r.threads, 0, s>>>(p);
+        what = "upfirdn2d(blur rows)";
+        break;
+    case gif_ew::FIR_BLUR_TILED:
+        blur4x4_tiled_kernel<T, 2, 4><<<grid, r.threads, 0, s>>>(p);
+        what = "upfirdn2d(blur)";
+        break;
+    case gif_ew::FIR_UP2_BLOCK:
+        fir4x4_up2_block_kernel<T><<<grid, r.threads, 0, s>>>(p);
+        what = "upfirdn2d(up 2, block)";
+        break;
+    case gif_ew::FIR_RESAMPLE:
+        if (r.DOWN == 2) fir4x4_resample_kernel<T, 1, 2><<<grid, r.threads, 0, s>>>(p);
+        else fir4x4_resample_kernel<T, 2, 1><<<grid, r.threads, 0, s>>>(p);
+        what = "upfirdn2d(resample by 2)";
+        break;
+    default:
+        upfirdn2d_kernel<T><<<grid, r.threads, 0, s>>>(p);
     }
-    if (blur) {
-        constexpr int TY = 2, TX = 4;
-        long total = (long)B * ((Ho + TY - 1) / TY) * ((Wo + TX - 1) / TX) * (C / 4);
-        const int grid = ew_grid(total);
-        blur4x4_tiled_kernel<T, TY, TX><<<grid, 256, 0, s>>>(p);
-        if (colsum_out) return gif::reduce_partials(p.part_cs, colsum_out, 1, grid, C, p.part_cs + (size_t)grid * C, s);
-        return gif::check_launch("upfirdn2d(blur)");
-    }
-    long total = (long)B * Ho * Wo * (C / 4);
-    if (KH == 4 && KW == 4 && (long)B * Ho <= 65535 && ((up == 1 && down == 2) || (up == 2 && down == 1))) {
-        // GIF_FIR_BLOCK=0: the one-pixel-per-lane kernel for up = 2 as well (A/B; the block kernel gives the same bits)
-        static const int block_on = gif::knob("GIF_FIR_BLOCK") ? atoi(gif::knob("GIF_FIR_BLOCK")) != 0 : 1;
-        if (block_on && up == 2) {
-            const long nby = (Ho + 2 - (pady0 & 1)) / 2, nbx = (Wo + 2 - (padx0 & 1)) / 2;
-            long gx = (nbx * (C / 4) + 255) / 256;
-            if (gx > 64) gx = 64;
-            const dim3 grid((unsigned)gx, (unsigned)((long)B * nby));
-            fir4x4_up2_block_kernel<T><<<grid, 256, 0, gif::as_stream(stream)>>>(p);
-            return gif::check_launch("upfirdn2d(up 2, block)");
-        }
-        const long row_items = (long)Wo * (C / 4);
-        long gx = (row_items + 255) / 256;
-        if (gx > 64) gx = 64;
-        const dim3 grid((unsigned)gx, (unsigned)((long)B * Ho));
-        if (down == 2) fir4x4_resample_kernel<T, 1, 2><<<grid, 256, 0, gif::as_stream(stream)>>>(p);
-        else fir4x4_resample_kernel<T, 2, 1><<<grid, 256, 0, gif::as_stream(stream)>>>(p);
-        return gif::check_launch("upfirdn2d(resample by 2)");
-    }
-    upfirdn2d_kernel<T><<<ew_grid(total), 256, 0, gif::as_stream(stream)>>>(p);
-    return gif::check_launch("upfirdn2d");
+    // red_ws (ew_route.h epilogue_ws_rows): the launch's partial rows from its start, the scratch of their reduction behind them; only
+    // the epilogue_tmp_rows that every red_ws has are counted on
+    if (colsum_out)
+        return gif::reduce_partials(p.part_cs, colsum_out, 1, r.partial_rows, C, p.part_cs + (size_t)r.partial_rows * C,
+                                    gif_ew::epilogue_tmp_rows() - r.partial_rows, s);
+    return gif::check_launch(what);
 }
 
 template <typename T>
@@ -782,7 +762,7 @@ int bias_act_impl(const T* x, const float* bias, const T* residual, T* y, int64_
     GIF_REQUIRE(x && y && npix >= 0 && C > 0 && C % 4 == 0, "bias_act: bad arguments (C=%d)", C);
     if (npix == 0) return 0;
     long n4 = npix * (C / 4);
-    bias_act_kernel<T><<<ew_grid(n4), 256, 0, gif::as_stream(stream)>>>(x, bias, residual, y, n4, C / 4, slope, gain);
+    bias_act_kernel<T><<<gif_ew::ew_grid(n4), 256, 0, gif::as_stream(stream)>>>(x, bias, residual, y, n4, C / 4, slope, gain);
     return gif::check_launch("bias_act");
 }
 
@@ -794,11 +774,11 @@ int bias_act_bwd_impl(const T* gy, const T* y, T* gx, float* gbias, float* parti
     if (npix == 0) return 0;
     hipStream_t s = gif::as_stream(stream);
     int C4 = C / 4;
-    int nblk = colsum_blocks(npix, C4);
-    long rpb = (npix + nblk - 1) / nblk;
+    int nblk = gif_ew::colsum_blocks(npix, C4);
+    long rpb = gif_ew::colsum_rows_per_block(npix, nblk);
     colsum_stage1<1, T><<<dim3(nblk, 1), 256, 0, s>>>(gy, y, gx, nullptr, partial, npix, C4, rpb, slope, gain, gbias != nullptr, nullptr, nullptr,
                                                        sizeof(T) == 2 ? gif::f16_sat_flag() : nullptr);
-    if (gbias) colsum_stage2<<<dim3(gif::cdiv(C, 64), 1), 256, 0, s>>>(partial, gbias, nblk, C);
+    if (gbias) colsum_stage2<<<dim3(gif_ew::reduce_channel_blocks(C), 1), 256, 0, s>>>(partial, gbias, nblk, C);
     return gif::check_launch("bias_act_bwd");
 }
 
@@ -807,10 +787,10 @@ int colsum_impl(const T* x, float* out, float* partial, int64_t npix, int C, gif
     GIF_REQUIRE(x && out && partial && npix >= 0 && C > 0 && C % 4 == 0 && C <= 1024, "colsum: bad arguments (C=%d)", C);
     hipStream_t s = gif::as_stream(stream);
     int C4 = C / 4;
-    int nblk = colsum_blocks(npix, C4);
-    long rpb = (npix + nblk - 1) / nblk;
+    int nblk = gif_ew::colsum_blocks(npix, C4);
+    long rpb = gif_ew::colsum_rows_per_block(npix, nblk);
     colsum_stage1<0, T><<<dim3(nblk, 1), 256, 0, s>>>(x, nullptr, nullptr, nullptr, partial, npix, C4, rpb, 0.f, 1.f, 1);
-    colsum_stage2<<<dim3(gif::cdiv(C, 64), 1), 256, 0, s>>>(partial, out, nblk, C);
+    colsum_stage2<<<dim3(gif_ew::reduce_channel_blocks(C), 1), 256, 0, s>>>(partial, out, nblk, C);
     return gif::check_launch("colsum");
 }
 
@@ -818,23 +798,15 @@ int colsum_impl(const T* x, float* out, float* partial, int64_t npix, int C, gif
 
 namespace gif {
 
-int reduce_partials(const float* partial, float* out, int Y, int nblk, int C, float* tmp, hipStream_t s) {
-    if (Y <= 0 || nblk <= 0) return 0;
-    if (Y == 1 && nblk > 512) {  // one long reduction: 64 groups first (two blocks of 64 channels alone would crawl through it)
-        const int S = 64, per = (nblk + S - 1) / S;
-        // groups of `per` rows; the last group may be short: pad by reducing [k*per, min((k+1)*per, nblk)) — stage 2 takes a row
-        // count per group, so run the full groups and the tail separately
-        const int full = nblk / per, tail = nblk - full * per;
-        colsum_stage2<<<dim3(cdiv(C, 64), full), 256, 0, s>>>(partial, tmp, per, C);
-        if (tail) colsum_stage2<<<dim3(cdiv(C, 64), 1), 256, 0, s>>>(partial + (size_t)full * per * C, tmp + (size_t)full * C, tail, C);
-        colsum_stage2<<<dim3(cdiv(C, 64), 1), 256, 0, s>>>(tmp, out, full + (tail ? 1 : 0), C);
-    } else if (Y > 1 && nblk >= 1024 && nblk % 16 == 0 && (long)Y * 16 <= 4096) {
-        // per-sample sums over thousands of rows (the halo kernels' one row per 16 x 16 patch at 1024^2): Y blocks alone would
-        // crawl; 16 groups per sample first (groups of one sample are consecutive rows of tmp)
-        colsum_stage2<<<dim3(cdiv(C, 64), Y * 16), 256, 0, s>>>(partial, tmp, nblk / 16, C);
-        colsum_stage2<<<dim3(cdiv(C, 64), Y), 256, 0, s>>>(tmp, out, 16, C);
-    } else {
-        colsum_stage2<<<dim3(cdiv(C, 64), Y), 256, 0, s>>>(partial, out, nblk, C);
+int reduce_partials(const float* partial, float* out, int Y, int nblk, int C, float* tmp, long tmp_rows, hipStream_t s) {
+    const gif_ew::ReducePlan plan = gif_ew::reduce_plan(Y, nblk);
+    if (!plan.nstages) return 0;
+    GIF_REQUIRE(plan.tmp_rows <= tmp_rows, "reduce_partials: %d x %d rows need %ld rows of scratch, the caller has %ld", Y, nblk, plan.tmp_rows,
+                tmp_rows);
+    for (int i = 0; i < plan.nstages; ++i) {
+        const gif_ew::ReduceStage& st = plan.stage[i];
+        colsum_stage2<<<dim3(gif_ew::reduce_channel_blocks(C), st.groups), 256, 0, s>>>((st.from_tmp ? tmp : partial) + (size_t)st.in_row * C,
+                                                                    (st.to_tmp ? tmp : out) + (size_t)st.out_row * C, st.per, C);
     }
     return check_launch("reduce_partials");
 }
@@ -842,8 +814,6 @@ int reduce_partials(const float* partial, float* out, int Y, int nblk, int C, fl
 }  // namespace gif
 
 namespace {
-
-inline int mul_reduce_chunks(int64_t HW) { return colsum_blocks(HW, 32) > 64 ? 64 : colsum_blocks(HW, 32); }
 
 template <typename T>
 int mul_reduce_impl(const T* a, const T* b, const float* scale, T* scaled, float* out, float* partial, int B, int64_t HW,
@@ -853,11 +823,11 @@ int mul_reduce_impl(const T* a, const T* b, const float* scale, T* scaled, float
     GIF_REQUIRE(!scaled || scale, "mul_reduce: scaled output needs scale");
     if (B == 0) return 0;
     hipStream_t s = gif::as_stream(stream);
-    int nchunk = mul_reduce_chunks(HW);
-    long rpb = (HW + nchunk - 1) / nchunk;
+    int nchunk = gif_ew::mul_reduce_chunks(HW);
+    long rpb = gif_ew::colsum_rows_per_block(HW, nchunk);
     colsum_stage1<2, T><<<dim3(nchunk, B), 256, 0, s>>>(a, b, scaled, scale, partial, HW, C / 4, rpb, 0.f, 1.f, 1, nullptr, nullptr,
                                                          sizeof(T) == 2 ? gif::f16_sat_flag() : nullptr);
-    colsum_stage2<<<dim3(gif::cdiv(C, 64), B), 256, 0, s>>>(partial, out, nchunk, C);
+    colsum_stage2<<<dim3(gif_ew::reduce_channel_blocks(C), B), 256, 0, s>>>(partial, out, nchunk, C);
     return gif::check_launch("mul_reduce");
 }
 
@@ -869,11 +839,11 @@ int act_inv_mul_reduce_impl(const T* g, const T* y, const T* residual, const flo
     GIF_REQUIRE(slope > 0.f && gain > 0.f, "act_inv_mul_reduce: activation must be invertible (slope, gain > 0)");
     if (B == 0) return 0;
     hipStream_t s = gif::as_stream(stream);
-    int nchunk = mul_reduce_chunks(HW);
-    long rpb = (HW + nchunk - 1) / nchunk;
+    int nchunk = gif_ew::mul_reduce_chunks(HW);
+    long rpb = gif_ew::colsum_rows_per_block(HW, nchunk);
     colsum_stage1<3, T><<<dim3(nchunk, B), 256, 0, s>>>(g, y, static_cast<T*>(nullptr), nullptr, partial, HW, C / 4, rpb, slope, gain,
                                                          1, residual, bias);
-    colsum_stage2<<<dim3(gif::cdiv(C, 64), B), 256, 0, s>>>(partial, out, nchunk, C);
+    colsum_stage2<<<dim3(gif_ew::reduce_channel_blocks(C), B), 256, 0, s>>>(partial, out, nchunk, C);
     return gif::check_launch("act_inv_mul_reduce");
 }
 
@@ -942,7 +912,7 @@ int pack_nhwc_impl(const float* src0, int C0, int off0, const int64_t* st0, cons
     PackSrc s0{src0, C0, off0, st0[0], st0[1], st0[2], st0[3]};
     PackSrc s1{src1, src1 ? C1 : 0, off1, src1 ? st1[0] : 0, src1 ? st1[1] : 0, src1 ? st1[2] : 0, src1 ? st1[3] : 0};
     const long npix = (long)B * H * W;
-    pack_nhwc_kernel<T><<<ew_grid(npix), 256, 0, gif::as_stream(stream)>>>(s0, s1, dst, H, W, Cp, npix, sizeof(T) == 2 ? gif::f16_sat_flag() : nullptr);
+    pack_nhwc_kernel<T><<<gif_ew::ew_grid(npix), 256, 0, gif::as_stream(stream)>>>(s0, s1, dst, H, W, Cp, npix, sizeof(T) == 2 ? gif::f16_sat_flag() : nullptr);
     return gif::check_launch("pack_nhwc");
 }
 
@@ -951,7 +921,7 @@ int unpack_nhwc_impl(const T* src, float* dst, int B, int H, int W, int Cp, int 
     GIF_REQUIRE(src && dst && B >= 0 && H > 0 && W > 0 && Cp > 0 && C > 0 && c_off >= 0 && c_off + C <= Cp, "unpack_nhwc: bad arguments");
     if (B == 0) return 0;
     const long npix = (long)B * H * W;
-    unpack_nhwc_kernel<T><<<ew_grid(npix), 256, 0, gif::as_stream(stream)>>>(src, dst, Cp, c_off, C, npix);
+    unpack_nhwc_kernel<T><<<gif_ew::ew_grid(npix), 256, 0, gif::as_stream(stream)>>>(src, dst, Cp, c_off, C, npix);
     return gif::check_launch("unpack_nhwc");
 }
 
@@ -983,12 +953,12 @@ int gif_bias_act_f16(const void* x, const float* bias, const void* residual, voi
 
 int64_t gif_conv_epilogue_ws_floats(int64_t out_rows, int cout) {
     if (out_rows <= 0 || cout <= 0) return 0;
-    return gif::epilogue_ws_rows(out_rows) * (int64_t)((cout + 3) / 4 * 4);
+    return gif_ew::epilogue_ws_rows(out_rows) * (int64_t)((cout + 3) / 4 * 4);
 }
 
 int64_t gif_colsum_partial_floats(int64_t npix, int C) {
     if (C <= 0 || C % 4 || C > 1024) return 0;
-    return (int64_t)colsum_blocks(npix, C / 4) * C;
+    return (int64_t)gif_ew::colsum_blocks(npix, C / 4) * C;
 }
 
 int gif_bias_act_bwd_f32(const float* gy, const float* y, float* gx, float* gbias, float* partial, int64_t npix, int C,
@@ -1008,7 +978,7 @@ int gif_colsum_f16(const void* x, float* out, float* partial, int64_t npix, int 
     return colsum_impl<gif::f16>(static_cast<const gif::f16*>(x), out, partial, npix, C, stream);
 }
 
-int gif_mul_reduce_chunks(int64_t HW) { return mul_reduce_chunks(HW); }
+int gif_mul_reduce_chunks(int64_t HW) { return gif_ew::mul_reduce_chunks(HW); }
 
 int gif_mul_reduce_f32(const float* a, const float* b, const float* scale, float* scaled, float* out, float* partial,
                        int B, int64_t HW, int C, gif_stream_t stream) {
@@ -1052,9 +1022,9 @@ int gif_bilinear_down_f32(const float* x, float* y, int B, int R, int S, int C, 
     if (B == 0) return 0;
     hipStream_t s = gif::as_stream(stream);
     if (!backward)
-        bilinear_down_kernel<<<ew_grid((long)B * S * S * (C / 4)), 256, 0, s>>>(x, y, B, R, S, C / 4);
+        bilinear_down_kernel<<<gif_ew::ew_grid((long)B * S * S * (C / 4)), 256, 0, s>>>(x, y, B, R, S, C / 4);
     else  // x = grad of the level [B,S,S,C], y = grad of the full-resolution condition [B,R,R,C]
-        bilinear_down_bwd_kernel<<<ew_grid((long)B * R * R * (C / 4)), 256, 0, s>>>(x, y, B, R, S, C / 4);
+        bilinear_down_bwd_kernel<<<gif_ew::ew_grid((long)B * R * R * (C / 4)), 256, 0, s>>>(x, y, B, R, S, C / 4);
     return gif::check_launch("bilinear_down");
 }
 
@@ -1066,7 +1036,7 @@ int gif_mbstd_fwd_f32(const float* x, float* y, float* stat, int B, int H, int W
     int M = B / G;
     mbstd_stat_kernel<<<M, 256, 0, s>>>(x, stat, M, G, (long)H * W * C);
     long total = (long)B * H * W * (Cy / 4);
-    mbstd_write_kernel<<<ew_grid(total), 256, 0, s>>>(x, stat, y, B, H * W, C, Cy, M);
+    mbstd_write_kernel<<<gif_ew::ew_grid(total), 256, 0, s>>>(x, stat, y, B, H * W, C, Cy, M);
     return gif::check_launch("mbstd_fwd");
 }
 
@@ -1153,22 +1123,17 @@ __global__ void __launch_bounds__(256) tex_pair_loss_bwd_kernel(const float* __r
     }
 }
 
-inline int tex_pair_blocks(long n) {
-    long b = (n + 255) / 256;
-    return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" {
 
-int gif_texture_pair_loss_partials(int64_t n) { return tex_pair_blocks(n); }
+int gif_texture_pair_loss_partials(int64_t n) { return gif_ew::tex_pair_blocks(n); }
 
 int gif_texture_pair_loss_f32(const float* a, const float* b, const uint8_t* ma, const uint8_t* mb, const float* f,
                               float* partial, float* loss, int C, int64_t HW, gif_stream_t stream) {
     GIF_REQUIRE(a && b && f && partial && loss && C > 0 && HW > 0, "texture_pair_loss: bad arguments");
     const long n = (long)C * HW;
-    const int nblk = tex_pair_blocks(n);
+    const int nblk = gif_ew::tex_pair_blocks(n);
     hipStream_t s = gif::as_stream(stream);
     tex_pair_loss_stage1<<<nblk, 256, 0, s>>>(a, b, ma, mb, f, partial, n, HW);
     tex_pair_loss_stage2<<<1, 256, 0, s>>>(partial, loss, nblk, 1.0f / (float)n);
@@ -1179,7 +1144,7 @@ int gif_texture_pair_loss_bwd_f32(const float* a, const float* b, const uint8_t*
                                   const float* gloss, float* ga, int C, int64_t HW, gif_stream_t stream) {
     GIF_REQUIRE(a && b && f && gloss && ga && C > 0 && HW > 0, "texture_pair_loss_bwd: bad arguments");
     const long n = (long)C * HW;
-    tex_pair_loss_bwd_kernel<<<tex_pair_blocks(n), 256, 0, gif::as_stream(stream)>>>(a, b, ma, mb, f, gloss, ga, n, HW,
+    tex_pair_loss_bwd_kernel<<<gif_ew::tex_pair_blocks(n), 256, 0, gif::as_stream(stream)>>>(a, b, ma, mb, f, gloss, ga, n, HW,
                                                                                       1.0f / (float)n);
     return gif::check_launch("texture_pair_loss_bwd");
 }

@@ -116,6 +116,7 @@ __global__ void __launch_bounds__(256) flame_skin_kernel(const float* __restrict
 // conflict-free) and used for every sample chunk.  Per chunk: g_v_posed of the tile into LDS, then lane = row k, wave = 8 samples.
 // Partial sums part[x][b][k]; gif::reduce_partials adds them over x in a fixed order.
 constexpr int kBV = 32, kBVC = 3 * kBV, kBK = 64;
+constexpr long kRedTmp = gif_ew::reduce_tmp_rows_single();  // scratch rows behind each region's partial rows (Y = 1 reductions)
 
 __global__ void __launch_bounds__(256) flame_skin_bwd_coef_kernel(const float* __restrict__ dirs, const float* __restrict__ lbs_w,
                                                                   const float* __restrict__ A, const float* __restrict__ g_verts,
@@ -397,8 +398,8 @@ extern "C" int gif_flame_skin_f32(const float* tmpl, const float* dirs, const fl
 
 extern "C" int64_t gif_flame_skin_bwd_workspace_bytes(int B, int V, int KP, int J) {
     if (!flame_dims_ok(B, V, KP, J) || B == 0 || V == 0) return 0;
-    // per region: the partial rows of its first pass + the 64 rows gif::reduce_partials may need for a long reduction
-    const int64_t coef_rows = gif::cdiv(V, kBV) + 64, a_rows = gif::cdiv(V, 64) + 64;
+    // per region: the partial rows of its first pass + the rows gif::reduce_partials may need for a long reduction
+    const int64_t coef_rows = gif::cdiv(V, kBV) + kRedTmp, a_rows = gif::cdiv(V, 64) + kRedTmp;
     return (coef_rows * B * KP + a_rows * B * J * 12) * (int64_t)sizeof(float);
 }
 
@@ -422,15 +423,15 @@ extern "C" int gif_flame_skin_bwd_f32(const float* dirs, const float* lbs_w, con
     GIF_REQUIRE(!g_A || v_posed, "flame_skin_bwd: g_A needs v_posed");
     float* ws = static_cast<float*>(workspace);
     const int nc = gif::cdiv(V, kBV), na = gif::cdiv(V, 64);
-    float* part_a = ws + (size_t)(nc + 64) * B * KP;
+    float* part_a = ws + (size_t)(nc + kRedTmp) * B * KP;
     if (g_coef && KP) {
         flame_skin_bwd_coef_kernel<<<dim3(nc, gif::cdiv(KP, kBK)), 256, 0, s>>>(dirs, lbs_w, A, g_verts, ws, B, V, KP, J);
-        int rc = gif::reduce_partials(ws, g_coef, 1, nc, B * KP, ws + (size_t)nc * B * KP, s);
+        int rc = gif::reduce_partials(ws, g_coef, 1, nc, B * KP, ws + (size_t)nc * B * KP, kRedTmp, s);
         if (rc) return rc;
     }
     if (g_A) {
         flame_skin_bwd_A_kernel<<<dim3(na, gif::cdiv(B, 4)), 256, 0, s>>>(lbs_w, g_verts, v_posed, part_a, B, V, J);
-        int rc = gif::reduce_partials(part_a, g_A, 1, na, B * J * 12, part_a + (size_t)na * B * J * 12, s);
+        int rc = gif::reduce_partials(part_a, g_A, 1, na, B * J * 12, part_a + (size_t)na * B * J * 12, kRedTmp, s);
         if (rc) return rc;
     }
     return gif::check_launch("flame_skin_bwd");

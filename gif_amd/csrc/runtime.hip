@@ -87,7 +87,7 @@ H2Gate h2_next_gate(hipStream_t s) {
     static unsigned* ccache[kMaxDevices] = {};
     static std::atomic<unsigned long long> next[kMaxDevices];
     static std::atomic<unsigned long long> cnext[kMaxDevices];
-    static const bool off = gif::knob("GIF_H2_GUARD") && atoi(gif::knob("GIF_H2_GUARD")) == 0;
+    static const bool off = gif::knob_int("GIF_H2_GUARD", 1) == 0;
     if (off) return {nullptr, 0, 0};
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) != hipSuccess) {

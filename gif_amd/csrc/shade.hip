@@ -223,8 +223,6 @@ __global__ void __launch_bounds__(256) shade_sh_bwd_kernel(const ShadeBwd a) {
             (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-// rows of scratch gif::reduce_partials may ask for: 64 (one long reduction) or 16 per sample (per-sample sums over >= 1024 rows)
-inline int64_t reduce_tmp_rows(int B) { return 64 + 16 * (int64_t)(B < 256 ? B : 256); }
 inline int bwd_blocks(int H, int W) { return gif::cdiv((long)H * W, 256 * kBwdRounds); }
 
 // the checks both entry points share; 1: nothing to do, 0: go on
@@ -251,7 +249,7 @@ extern "C" int gif_shade_sh_f32(const float* uv, const float* nrm, const uint8_t
 
 extern "C" int64_t gif_shade_sh_bwd_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return ((int64_t)B * bwd_blocks(H, W) + reduce_tmp_rows(B)) * 27 * (int64_t)sizeof(float);
+    return ((int64_t)B * bwd_blocks(H, W) + gif_ew::reduce_tmp_rows(B)) * 27 * (int64_t)sizeof(float);
 }
 
 extern "C" int gif_shade_sh_bwd_f32(const float* uv, const float* nrm, const uint8_t* mask, const float* albedo,
@@ -282,6 +280,6 @@ extern "C" int gif_shade_sh_bwd_f32(const float* uv, const float* nrm, const uin
     a.HW = H * W; a.nblk = bwd_blocks(H, W); a.per_sample_albedo = Ba == B; a.T = T; a.nrm_mul = nrm_mul; a.nrm_add = nrm_add;
     shade_sh_bwd_kernel<<<(unsigned)((int64_t)a.nblk * B), 256, 0, s>>>(a);
     if (int e = gif::check_launch("shade_sh_bwd")) return e;
-    if (g_sh) return gif::reduce_partials(a.part, g_sh, B, a.nblk, 27, a.part + (size_t)B * a.nblk * 27, s);
+    if (g_sh) return gif::reduce_partials(a.part, g_sh, B, a.nblk, 27, a.part + (size_t)B * a.nblk * 27, gif_ew::reduce_tmp_rows(B), s);
     return 0;
 }

@@ -451,8 +451,8 @@ FIR_ROWS = [
     # The colsum reduces one partial row per workgroup: reduce_partials(Y = 1, nblk = grid): nblk > 512 -> 64 groups (+ a tail group)
     FirRow("blur_tiled_small", 2, 8, 38, 42, 1, 1, 1, (37, 41), "fuse"),    # tiled, grid 4: single-stage reduction
     FirRow("blur_tiled_tail", 1, 4, 261, 4097, 1, 1, 1, (260, 4096), "fuse"),  # tiled total 133120: grid 520 -> per 9, 57 groups + tail 7
-    FirRow("blur_tiled_131008", 1, 4, 1025, 8189, 1, 1, 1, (1024, 8188), "fuse"),  # rows total 131008 < 131072 -> tiled; grid 4096:
-                                                                                    #   per 64, 64 groups, no tail
+    FirRow("blur_tiled_131008", 1, 4, 1025, 8189, 1, 1, 1, (1024, 8188), "fuse"),  # rows total 131008 < 131072 -> tiled; grid 4094:
+                                                                                    #   per 64, 63 groups + tail 62
     FirRow("blur_rows_131072", 1, 4, 1025, 8190, 1, 1, 1, (1024, 8189), "fuse"),   # 131072 -> rows kernel; grid 512: single stage
     FirRow("blur_rows_513", 1, 4, 1025, 8194, 1, 1, 1, (1024, 8193), "fuse"),      # 131136 -> grid 513: 57 groups of 9, no tail
     FirRow("blur_rows_tail", 1, 4, 1041, 8190, 1, 1, 1, (1040, 8189), "fuse"),     # 133120 -> grid 520: 57 groups + tail 7
