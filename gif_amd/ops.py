@@ -76,7 +76,35 @@ def nhwc(x: torch.Tensor) -> torch.Tensor:
         raise _lib.GifHipError(f"expected a 4-D activation, got shape {tuple(x.shape)}")
     if x.dtype == torch.float16 and x.shape[1] % 8:
         raise _lib.GifHipError(f"f16 activations need a channel count that is a multiple of 8, got {x.shape[1]}")
-    return x.contiguous(memory_format=CL)
+    return _aligned(x.contiguous(memory_format=CL))
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """`t` (dense in its own layout) at a 16-byte-aligned address: the kernels read operands as 16-byte lanes.  A dense view that starts
+    an odd number of elements into a larger buffer is copied; fresh allocations never are."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.preserve_format)
+
+
+def _vec(t: Optional[torch.Tensor], what: str, shape, device) -> Optional[torch.Tensor]:
+    """A per-channel ([C]) or per-sample ([B,C]) operand, FIR taps included, as the kernels index it: fp32, on `device`, exactly `shape`
+    (the ACTIVATION's channel count: layers._pad_vec), dense and 16-byte aligned (any other strides or offset: a copy of a few hundred
+    floats).  Another dtype is refused, not converted: a cast inside a Function would hand autograd a gradient of the wrong dtype."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != device or tuple(t.shape) != tuple(shape):
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise _lib.GifHipError(f"{what}: expected an fp32 tensor of shape {tuple(shape)} on {device}, got {got}")
+    return _aligned(t.contiguous())
+
+
+def _weight_check(w, device, what: str):
+    """A convolution weight is a 4-D fp32 tensor (any strides) on the activations' device: the packing kernels read it as floats through
+    its address and element strides."""
+    if (not isinstance(w, torch.Tensor) or w.dim() != 4 or w.dtype != torch.float32 or not w.is_cuda
+            or (device is not None and w.device != device)):
+        got = f"{tuple(w.shape)} {w.dtype} on {w.device}" if isinstance(w, torch.Tensor) else type(w).__name__
+        raise _lib.GifHipError(f"{what}: weight: expected a 4-D fp32 tensor on {device or 'the device'} (no CPU fallback, no conversion), "
+                               f"got {got}")
 
 
 def _same_dtype(a, b, what):
@@ -134,19 +162,33 @@ def dot_fusable(H, W, dtype=torch.float32):
 
 
 def _epilogue(in_scale=None, out_scale=None, bias=None, residual=None, act=False, slope=0.2, gain=2 ** 0.5, fuse=None,
-              out_bchw=None, dtype=torch.float32, out_f32=False):
+              out_bchw=None, dtype=torch.float32, out_f32=False, in_c=None, device=None):
+    """The gif_conv_epilogue of a launch that writes an activation of shape out_bchw and element type `dtype` on `device` (in_c: channel
+    count of the activation it reads).  in_scale [B,in_c], out_scale [B,C] and bias [C] go through _vec; residual, mask_src and dot_src must
+    be NHWC tensors of the output's shape and dtype at a 16-byte-aligned address (ops.nhwc gives one).  The dense copies _vec made stay
+    alive on the returned struct until the caller has launched."""
+    B, C, H, W = out_bchw
+    if device is None:  # (a caller that names none: the device of the first operand there is)
+        given = [t for t in (residual, in_scale, out_scale, bias, *((fuse.mask_src, fuse.dot_src) if fuse is not None else ()))
+                 if isinstance(t, torch.Tensor)]
+        device = given[0].device if given else None
+    in_scale = _vec(in_scale, "conv epilogue: in_scale", (B, C if in_c is None else in_c), device)
+    out_scale = _vec(out_scale, "conv epilogue: out_scale", (B, C), device)
+    bias = _vec(bias, "conv epilogue: bias", (C,), device)
+    for t, what, dt in ((residual, "conv epilogue: residual", dtype), (None if fuse is None else fuse.mask_src, "GradFuse.mask_src", dtype),
+                        (None if fuse is None else fuse.dot_src, "GradFuse.dot_src", dtype)):
+        if t is not None and (tuple(t.shape) != (B, C, H, W) or t.dtype != dt or t.device != device or not t.is_contiguous(memory_format=CL)
+                              or t.data_ptr() % 16):
+            raise _lib.GifHipError(f"{what}: expected a 16-byte-aligned NHWC {dt} tensor of shape {(B, C, H, W)} on {device}, got "
+                                   f"{tuple(t.shape)} {t.dtype} on {t.device}, strides {tuple(t.stride())}")
     e = _lib.ConvEpilogue(_p(in_scale), _p(out_scale), _p(bias), _p(residual), 1 if act else 0, slope, gain)
+    e._keep = (in_scale, out_scale, bias)
     e.out_f32 = 1 if out_f32 else 0
     if fuse is not None:
-        B, C, H, W = out_bchw
-        for t, what in ((fuse.mask_src, "mask_src"), (fuse.dot_src, "dot_src")):
-            if t is not None and (tuple(t.shape) != (B, C, H, W) or t.dtype != dtype or not t.is_contiguous(memory_format=CL)):
-                raise _lib.GifHipError(f"GradFuse.{what}: expected an NHWC {dtype} tensor of shape {(B, C, H, W)}, got {tuple(t.shape)} {t.dtype}")
         e.mask_src, e.mask_slope, e.mask_gain = _p(fuse.mask_src), fuse.mask_slope, fuse.mask_gain
         e.dot_src = _p(fuse.dot_src)
         if fuse.mask_src is None and fuse.dot_src is None:
             raise _lib.GifHipError("GradFuse: nothing to fuse (the plain column sum of a gradient is ops.colsum)")
-        device = fuse.mask_src.device if fuse.mask_src is not None else fuse.dot_src.device
         if fuse.dot_src is not None:
             fuse.dot = torch.empty((B, C), device=device, dtype=torch.float32)
             e.dot = fuse.dot.data_ptr()
@@ -258,8 +300,10 @@ def _dims(query, rows: int, cols: int, what: str):
     return RP.value, CP.value
 
 
-def _pack(w, rows_are_out, cout_act, cin_act, scale, dtype, form, tapdense):
-    """pack_weight / pack_weight_h2x3: `form` is the family of gif_pack_weight_<form>[_tapdense] ("f32h2x3": both operands of an f16x2 launch)."""
+def _pack(w, rows_are_out, cout_act, cin_act, scale, dtype, form, tapdense, device=None):
+    """pack_weight / pack_weight_h2x3: `form` is the family of gif_pack_weight_<form>[_tapdense] ("f32h2x3": both operands of an f16x2 launch).
+    device: the activations' (None: a device weight on its own)."""
+    _weight_check(w, device, "pack_weight")
     lib = _lib.load()
     KH, KW = w.shape[2:]
     R, C, sr, sc, sky, skx = _weight_view(w, rows_are_out, cout_act, cin_act)
@@ -283,7 +327,7 @@ def _pack(w, rows_are_out, cout_act, cin_act, scale, dtype, form, tapdense):
 
 
 def pack_weight(w: torch.Tensor, rows_are_out: bool, cout_act: int, cin_act: int, scale: float = 1.0, dtype=torch.float32, x3=False,
-                tapdense=False, h2=False):
+                tapdense=False, h2=False, device=None):
     """Pack a canonical forward-conv weight view w[O,I,KH,KW] (any strides) into [T][RP][CP] of `dtype` (fp32 or f16), or
     (x3=True) into the pre-split bf16x3 operand [T][3][RP][CP] (bf16) of the gif_conv2d_*_f32x3 entry points, (tapdense=True) into that
     operand in the tap-dense K order [steps][3][RP][32], or (h2=True) into the f16x2 operand.
@@ -293,12 +337,12 @@ def pack_weight(w: torch.Tensor, rows_are_out: bool, cout_act: int, cin_act: int
     cout_act / cin_act are the channel counts of the op's output / input ACTIVATIONS (>= canonical counts).
     """
     form = "f32x3" if tapdense else "f32h2" if h2 else "f32x3" if x3 else "f16" if dtype == torch.float16 else "f32"
-    return _pack(w, rows_are_out, cout_act, cin_act, scale, dtype, form, tapdense)
+    return _pack(w, rows_are_out, cout_act, cin_act, scale, dtype, form, tapdense, device)
 
 
-def pack_weight_h2x3(w: torch.Tensor, rows_are_out: bool, cout_act: int, cin_act: int, scale: float = 1.0, tapdense=False):
+def pack_weight_h2x3(w: torch.Tensor, rows_are_out: bool, cout_act: int, cin_act: int, scale: float = 1.0, tapdense=False, device=None):
     """(wp2, wp3): the f16x2 packing and the bf16x3 packing (the guarded fallback's operand) of the same weight view, ONE launch."""
-    return _pack(w, rows_are_out, cout_act, cin_act, scale, torch.float32, "f32h2x3", tapdense)
+    return _pack(w, rows_are_out, cout_act, cin_act, scale, torch.float32, "f32h2x3", tapdense, device)
 
 
 # Winograd F(2x2,3x3) dispatch for stride-1 / pad-1 3x3 convs (conv_winograd.hip).  GIF_WINOGRAD=0 forces the direct
@@ -417,9 +461,11 @@ def conv3x3_winograd(x, w, rows_are_out: bool, cout_act: int, wscale=1.0, keep_v
     _winograd_calls += 1
     lib = _lib.load()
     x = nhwc(x)
+    _weight_check(w, x.device, "conv3x3_winograd")
     B, C, H, W = x.shape
     R, Cc, sr, sc, sky, skx = _weight_view(w, rows_are_out, cout_act, C)
     mode = winograd_mode("fwd", cout_act)
+    e = _epilogue(out_bchw=(B, cout_act, H, W), in_c=C, device=x.device, **epi)  # (before anything is launched or cached: it refuses)
 
     def build():  # f16x2: its transform and the bf16x3 transform (the operand of the GEMM's guarded bf16x3 twin) in one launch
         RP, CP = _dims(lib.gif_winograd_pack_dims if mode == "native" else lib.gif_winograd_pack_dims_x3, cout_act, C, "winograd_pack_dims")
@@ -433,7 +479,6 @@ def conv3x3_winograd(x, w, rows_are_out: bool, cout_act: int, wscale=1.0, keep_v
     U = _cached_weight_op(w, ("wino", rows_are_out, cout_act, C, float(wscale), mode), build)
     V = torch.empty((lib.gif_winograd_workspace_floats(B, H, W, C),), device=x.device, dtype=torch.float32)
     out = empty_nhwc(B, cout_act, H, W, x.device)
-    e = _epilogue(out_bchw=(B, cout_act, H, W), **epi)
     _call("conv3x3_winograd", mode, x.data_ptr(), *_weight_ptrs(U), out.data_ptr(), V.data_ptr(), B, H, W, C, cout_act, ctypes.byref(e), _stream())
     return (out, V) if keep_v else out
 
@@ -448,13 +493,13 @@ def _conv_direct(plan: ConvPlan, op: str, src, w, out_bchw, g, wscale, epi):
     """The direct-kernel launch of conv_fwd (op "conv2d_fwd") / conv_bwd_data ("conv2d_bwd_data") as `plan` says: weights packed for the
     plan's mode (an f16x2 launch takes the bf16x3 packing for its guarded fallback too), then the one entry point."""
     fwd, dt = op == "conv2d_fwd", src.dtype
+    e = _epilogue(out_bchw=out_bchw, dtype=dt, in_c=src.shape[1], device=src.device, **epi)  # (before anything is launched or cached: it refuses)
     if plan.mode == "f16x2":
-        wp = pack_weight_h2x3(w, fwd, out_bchw[1], src.shape[1], wscale, tapdense=plan.dense)
+        wp = pack_weight_h2x3(w, fwd, out_bchw[1], src.shape[1], wscale, tapdense=plan.dense, device=src.device)
     else:
-        wp = pack_weight(w, fwd, out_bchw[1], src.shape[1], wscale, dt, x3=plan.mode == "bf16x3", tapdense=plan.dense)
+        wp = pack_weight(w, fwd, out_bchw[1], src.shape[1], wscale, dt, x3=plan.mode == "bf16x3", tapdense=plan.dense, device=src.device)
     # out_f32 (f16 activations only): fp32 result, e.g. the RGB image of ToRGB
     out = empty_nhwc(*out_bchw, src.device, torch.float32 if epi.get("out_f32") else dt)
-    e = _epilogue(out_bchw=out_bchw, dtype=dt, **epi)
     _call(op, plan.mode, src.data_ptr(), *_weight_ptrs(wp), out.data_ptr(), ctypes.byref(g), ctypes.byref(e), _stream(), dense=plan.dense)
     return out
 
@@ -465,6 +510,7 @@ def conv_fwd(big, w, spec: ConvSpec, wscale=1.0, keep_v=False, **epi):
     keep_v=True returns (small, V) where V is the Winograd-transformed (in_scale * big) if that path ran, else None;
     pass it to conv_wgrad(big_v=V) for the weight gradient of the same (big, in_scale)."""
     big = nhwc(big)
+    _weight_check(w, big.device, "conv_fwd")
     dt = big.dtype
     B, Cb, Hb, Wb = big.shape
     Cs = cpad(w.shape[0], dt)
@@ -482,6 +528,7 @@ def conv_fwd(big, w, spec: ConvSpec, wscale=1.0, keep_v=False, **epi):
 def conv_bwd_data(small, w, spec: ConvSpec, big_hw, wscale=1.0, **epi):
     """big = conv_transpose2d(small, w[O,I,KH,KW]) ; returns [B, cpad(I), Hb, Wb] in small's dtype."""
     small = nhwc(small)
+    _weight_check(w, small.device, "conv_bwd_data")
     dt = small.dtype
     B, Cs, Hs, Ws = small.shape
     Cb = cpad(w.shape[1], dt)
@@ -507,6 +554,8 @@ def conv3x3_winograd_wgrad(small, big, O, I, wscale=1.0, small_scale=None, big_s
     B, Cs, H, W = small.shape
     Cb = big.shape[1]
     assert big.shape == (B, Cb, H, W) and O <= Cs and I <= Cb
+    small_scale = _vec(small_scale, "conv3x3_winograd_wgrad: small_scale", (B, Cs), small.device)
+    big_scale = _vec(big_scale, "conv3x3_winograd_wgrad: big_scale", (B, Cb), small.device)
     RP, CP = _dims(lib.gif_conv2d_wgrad_dims, pad32(Cs), pad32(Cb), "wgrad_dims")
     nsplit = lib.gif_conv3x3_winograd_wgrad_splits(B, H, W, Cs, Cb)
     dev = small.device
@@ -534,6 +583,8 @@ def conv_wgrad(small, big, spec: ConvSpec, O, I, wscale=1.0, small_scale=None, b
     B, Cs, Hs, Ws = small.shape
     _, Cb, Hb, Wb = big.shape
     assert O <= Cs and I <= Cb
+    small_scale = _vec(small_scale, "conv_wgrad: small_scale", (B, Cs), small.device)
+    big_scale = _vec(big_scale, "conv_wgrad: big_scale", (B, Cb), small.device)
     plan = conv_plan("wgrad", small.dtype, B, spec, (Hb, Wb), (Hs, Ws), Cb, Cs)
     if plan.route == "winograd":
         return conv3x3_winograd_wgrad(small, big, O, I, wscale, small_scale, big_scale, big_v)
@@ -561,12 +612,16 @@ def upfirdn2d(x, k, up, down, pad0, out_hw, flip=True, bias=None, residual=None,
     x = nhwc(x)
     B, C, Hi, Wi = x.shape
     Ho, Wo = out_hw
+    if not isinstance(k, torch.Tensor) or k.dim() != 2:
+        raise _lib.GifHipError(f"upfirdn2d: k: expected 2-D FIR taps, got {tuple(k.shape) if isinstance(k, torch.Tensor) else type(k).__name__}")
     KH, KW = k.shape
-    k = k.contiguous()
+    k = _vec(k, "upfirdn2d: k (FIR taps)", (KH, KW), x.device)
     if residual is not None:
+        residual = nhwc(residual)  # (any layout a caller has: an NCHW tensor of the right shape is not NHWC memory)
         _same_dtype(x, residual, "upfirdn2d residual")
+    e = _epilogue(bias=bias, residual=residual, act=act, slope=slope, gain=gain, fuse=fuse, out_bchw=(B, C, Ho, Wo), dtype=x.dtype,
+                  device=x.device)
     y = empty_nhwc(B, C, Ho, Wo, x.device, x.dtype)
-    e = _epilogue(bias=bias, residual=residual, act=act, slope=slope, gain=gain, fuse=fuse, out_bchw=(B, C, Ho, Wo), dtype=x.dtype)
     _lib.check(_fn("upfirdn2d", x.dtype)(x.data_ptr(), k.data_ptr(), y.data_ptr(), B, Hi, Wi, C, Ho, Wo, up, down, pad0, pad0,
                                          KH, KW, 1 if flip else 0, ctypes.byref(e), _stream()), "upfirdn2d")
     return y
@@ -577,8 +632,10 @@ def bias_act(x, bias=None, residual=None, slope=0.2, gain=2 ** 0.5):
     B, C, H, W = x.shape
     if residual is not None:
         residual = nhwc(residual)
-        assert residual.shape == x.shape
+        if residual.shape != x.shape or residual.device != x.device:
+            raise _lib.GifHipError(f"bias_act: residual: expected shape {tuple(x.shape)} on {x.device}, got {tuple(residual.shape)} on {residual.device}")
         _same_dtype(x, residual, "bias_act residual")
+    bias = _vec(bias, "bias_act: bias", (C,), x.device)
     y = empty_nhwc(B, C, H, W, x.device, x.dtype)
     _lib.check(_fn("bias_act", x.dtype)(x.data_ptr(), _p(bias), _p(residual), y.data_ptr(), B * H * W, C, slope, gain,
                                         _stream()), "bias_act")
@@ -630,9 +687,7 @@ def mul_reduce(a, b, scale=None, want_scaled=False):
     out = torch.empty((B, C), device=a.device, dtype=torch.float32)
     partial = torch.empty((B * nchunk * C,), device=a.device, dtype=torch.float32)
     scaled = empty_nhwc(B, C, H, W, a.device, a.dtype) if want_scaled else None
-    if scale is not None:
-        scale = scale.contiguous()
-        assert scale.shape == (B, C) and scale.dtype == torch.float32
+    scale = _vec(scale, "mul_reduce: scale", (B, C), a.device)
     _lib.check(_fn("mul_reduce", a.dtype)(a.data_ptr(), b.data_ptr(), _p(scale), _p(scaled), out.data_ptr(), partial.data_ptr(),
                                           B, H * W, C, _stream()), "mul_reduce")
     return out, scaled
@@ -694,6 +749,12 @@ def act_inv_mul_reduce(g, y, residual, bias, slope, gain):
     g, y = nhwc(g), nhwc(y)
     _same_dtype(g, y, "act_inv_mul_reduce")
     B, C, H, W = y.shape
+    bias = _vec(bias, "act_inv_mul_reduce: bias", (C,), y.device)
+    if residual is not None:
+        residual = nhwc(residual)
+        if residual.shape != y.shape or residual.device != y.device:
+            raise _lib.GifHipError(f"act_inv_mul_reduce: residual: expected shape {tuple(y.shape)} on {y.device}, got {tuple(residual.shape)}")
+        _same_dtype(y, residual, "act_inv_mul_reduce residual")
     if B * H * W == 0:  # nothing to launch
         return torch.zeros((B, C), device=y.device, dtype=torch.float32)
     nchunk = lib.gif_mul_reduce_chunks(H * W)
@@ -848,7 +909,9 @@ del _name
 def _mat(t, what):
     if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
         raise _lib.GifHipError(f"{what}: need a 2-D fp32 device tensor (no CPU fallback), got {tuple(t.shape)} {t.dtype} on {t.device}")
-    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 else t.contiguous()
+    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0:
+        return t
+    return _aligned(t.contiguous())  # (.contiguous() alone hands a dense matrix at an odd offset back as it is)
 
 
 def linear_nt(a, b, bias=None, scale=1.0, act=False, slope=0.2, gain=1.0, n_pad=None):
@@ -859,6 +922,8 @@ def linear_nt(a, b, bias=None, scale=1.0, act=False, slope=0.2, gain=1.0, n_pad=
     N, K = b.shape
     assert a.shape[1] >= K, (a.shape, b.shape)  # `a` may carry padding columns beyond K
     n_pad = N if n_pad is None else n_pad
+    # (the kernel reads bias[n] for n < N only: the logical width is taken as well as the padded one EqualLinear passes)
+    bias = _vec(bias, "linear_nt: bias", (N,) if bias is not None and tuple(bias.shape) == (N,) else (n_pad,), a.device)
     c = torch.empty((M, n_pad), device=a.device, dtype=torch.float32)
     _lib.check(lib.gif_linear_nt_f32(a.data_ptr(), b.data_ptr(), _p(bias), c.data_ptr(), M, N, K, a.stride(0), b.stride(0), n_pad,
                                      n_pad, float(scale), 1 if act else 0, float(slope), float(gain), _stream()), "linear_nt")

@@ -418,6 +418,11 @@ int gif_shade_sh_bwd_f32(const float* uv, const float* nrm, const uint8_t* mask,
  * INPUT channels, zero padded to the tile sizes reported by gif_conv2d_pack_dims(); tap index is always
  * the forward conv's ky*KW+kx.  Optional per-sample scales implement weight (de)modulation without
  * materialising per-sample weights:  y = act(out_scale[b,co] * conv(in_scale[b,ci] * x) + residual + bias).
+ * Alignment: every activation, residual, mask_src / dot_src, per-channel and per-sample vector, packed weight and workspace pointer of
+ * the conv-side entry points (conv, FIR, bias / activation, reductions, minibatch stddev, style path) must be 16-byte aligned and
+ * dense — the kernels read them as 16-byte lanes; Cin / Cout of in_scale, out_scale and bias are the ACTIVATIONS' channel counts.
+ * Only the SOURCE weight of gif_pack_weight_* / gif_winograd_weight_* is read one float at a time through its element strides and
+ * needs no more than a float's alignment.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t B;

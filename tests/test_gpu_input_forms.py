@@ -127,11 +127,16 @@ def build(form, x, dense):
 
 class recorded_launches:
     """Context: every call of a gif_* symbol through _lib.load() is recorded as (name, arguments) in .calls.  The bindings fetch the
-    library with _lib.load() at every call, so swapping the loaded handle for a forwarding proxy sees all of them."""
+    library with _lib.load() at every call, so swapping the loaded handle for a forwarding proxy sees all of them.
+    before(name, args), if given, is called BEFORE the call is recorded and forwarded: a hook that raises keeps the arguments from ever
+    reaching the library (tests/ops_forms.py: `checked`, `forbidden`)."""
+
+    def __init__(self, before=None):
+        self.before = before
 
     def __enter__(self):
         from gif_amd import _lib
-        real, calls = _lib.load(), []
+        real, calls, before = _lib.load(), [], self.before
 
         class Proxy:
             def __getattr__(self, name):
@@ -140,6 +145,8 @@ class recorded_launches:
                     return fn
 
                 def call(*args):
+                    if before is not None:
+                        before(name, args)
                     calls.append((name, args))
                     return fn(*args)
                 return call
